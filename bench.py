@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — BASELINE.json's metric on MI355X: effective TFLOPS (2*M*N*K) + tokens/s of the Q4_K MUL_MAT hot path.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|c5] [--variant V --splitk S (kernel knobs, 0 = auto)]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|c5] [--variant V --splitk S (kernel knobs, 0 = auto)] [--full] [--dump-outputs DIR]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...; one rank per GPU, RCCL.
    Started WITHOUT a launcher — `python bench.py --gpus N`, WORLD_SIZE unset — it re-executes itself under torch.distributed.run with N ranks: round 6.)
 
@@ -13,14 +13,17 @@ config headline (default; the shape the metric is quoted on, BASELINE configs[1]
 config c5 (BASELINE configs[4]): Q4_K [32768x8192]·[8192x512] STRONG scaling: rank r owns rows [32768 r / N, 32768 (r+1) / N);
     value = 2*32768*8192*512 / (max-over-ranks time); also reported with the RCCL all-gather of the output (fp32 and fp16) and
     as the K-split variant (rank r owns whole superblocks [r K/N, (r+1) K/N) of every row, RCCL all-reduce of the partial
-    outputs) whose result is CHECKED against the row-split result.  A default multi-GPU run also carries the c5 numbers ("c5").
+    outputs) whose result is CHECKED against the row-split result.  A --full multi-GPU run also carries the c5 numbers ("c5").
 Inputs (SURVEY.md §8(d)): W = fp32 uniform(-1,1) from std::mt19937(1234) through the reference's ggml_quantize_chunk, X =
     uniform(-1,1) from mt19937(4321) — produced by oracle/_ref/synth_data (measurement infrastructure, never in the timed
     region); when that binary is absent the weights are random VALID blocks and "data" says so.
-Beside the metric: roofline of the dominant kernel (HIP events on the launch stream) with the vendor library's fp16 GEMM of the
-same shape as "library_ceiling", the C3 / C5 shapes, the decode GEMV (4096x4096 and the reference's perf shape 4096x14336),
-all weight formats, the reference CPU backend on the host cores (thread sweep, AVX2 and AVX-512 builds), the stock
-test-backend-ops perf lines for the plug-in.  oracle/ is touched only by the cpu_baseline / synth legs.
+A plain run sets up, warms up, times the --steps steps and prints the JSON line.  --dump-outputs DIR writes the output of
+the last timed step (y: [B][M] fp32, this rank's shard) as DIR/<name>.npy; the inputs are seeded, so runs with the same
+arguments can be compared output for output.
+With --full, beside the metric: roofline of the dominant kernel (HIP events on the launch stream) with the vendor library's
+fp16 GEMM of the same shape as "library_ceiling", the C3 / C5 shapes, the decode GEMV (4096x4096 and the reference's perf
+shape 4096x14336), all weight formats, the reference CPU backend on the host cores (thread sweep, AVX2 and AVX-512 builds),
+the stock test-backend-ops perf lines for the plug-in.  oracle/ is touched only by the cpu_baseline / synth legs.
 """
 import argparse
 import json
@@ -42,6 +45,7 @@ Q4_K = 12
 HEAD = (4096, 4096, 512)           # M per GPU, K, B
 C5 = (32768, 8192, 512)
 REFDIR = os.path.join(ROOT, "oracle", "_ref")
+DUMP_BYTES = 48 << 20              # --dump-outputs writes at most this much, over all ranks
 T_START = time.time()
 
 
@@ -646,8 +650,8 @@ def stock_perf_lines(timeout=150):
 
 
 # ------------------------------------------------------------------------------------------------ multi-GPU legs
-def c5_leg(dist, dev, rank, world, steps, warmup):
-    """BASELINE configs[4]: Q4_K [32768x8192]·[8192x512], strong scaling over the ranks (see module doc)"""
+def c5_leg(dist, dev, rank, world, steps, warmup, dump=None):
+    """BASELINE configs[4]: Q4_K [32768x8192]·[8192x512], strong scaling over the ranks (see module doc); dump = --dump-outputs of the compute_only loop"""
     M, K, B = C5
     lo, hi = M * rank // world, M * (rank + 1) // world
     w, x, how = prescribed(Q4_K, M, K, lo, hi, B)
@@ -677,6 +681,8 @@ def c5_leg(dist, dev, rank, world, steps, warmup):
     flops = 2.0 * M * K * B
     out = {"workload": "Q4_K [32768x8192]·[8192x512] row-sharded over %d GPU(s), strong scaling" % world, "data": how}
     ms = timed(h.step)
+    if dump:
+        dump_outputs(dump, {"y" if world == 1 else "y_rank%d" % rank: h.y}, DUMP_BYTES // world)
     out["compute_only"] = {"ms_per_step": round(ms, 5), "tflops": round(flops / ms / 1e9, 2), "frac_of_n_gpu_roof": round(flops / ms / 1e9 / (MFMA_F16_PEAK_TFLOPS * world), 4),
                            "what": "each rank: quantize + GEMM over its %d rows; output left sharded (the consumer of a row-split layer reads its own shard)" % (hi - lo)}
     if dist is not None:
@@ -707,6 +713,17 @@ def c5_leg(dist, dev, rank, world, steps, warmup):
         out["accounting"] = ("compute_only is the number the >= 6x target of the north star can refer to (output left sharded); gathering the fp32 output moves "
                              "%.1f MB per rank over xGMI (>= %.0f us at 153 GB/s per link), the fp16 gather half of that" % (B * (hi - lo) * 4 / 1e6, B * (hi - lo) * 4 / 153e3))
     return out
+
+
+def dump_outputs(d, arrays, budget):
+    """--dump-outputs: each array as d/<name>.npy in float32; an array above its share of the byte budget is cut to a fixed sample of its
+    columns (every s-th output feature)"""
+    os.makedirs(d, exist_ok=True)
+    share = budget // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        s = -(-a.nbytes // share)
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a[..., ::s]) if s > 1 else a)
 
 
 def leg_in_child(name, steps, timeout):
@@ -758,15 +775,19 @@ def main():
     ap.add_argument("--config", default="headline", choices=["headline", "c5"])
     ap.add_argument("--variant", type=int, default=0)
     ap.add_argument("--splitk", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the metric, its roofline, the library ceiling and the CPU baseline")
+    ap.add_argument("--full", action="store_true", help="everything beside the metric: the roofline and its kernel-only loops, the library ceiling, the CPU baseline, "
+                                                        "the other shapes, formats and legs; with N > 1 the collective legs and C5.  Without it a run times the steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) no CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="(with --full) only the metric, its roofline, the library ceiling and the CPU baseline")
     ap.add_argument("--no-diagnostics", action="store_true", help="(accepted for compatibility; same as --no-extras)")
     ap.add_argument("--leg", default=None, help="(internal) run ONE optional leg in this process and print its JSON: the parent runs legs that touch "
                                                 "paths without a hardware session of their own this way, so that a device fault there cannot take the metric line down")
     ap.add_argument("--lean", action="store_true", help="profiling runs (scripts/gpu_full.sh): the timed loop and the kernel-only loop, nothing else — every launch of the "
                                                         "dominant kernel in the trace is a headline launch on the prescribed data")
     args = ap.parse_args()
-    extras = not (args.no_extras or args.no_diagnostics or args.lean)
+    full = args.full or args.lean
+    extras = full and not (args.no_extras or args.no_diagnostics or args.lean)
     if args.lean:
         args.no_cpu_baseline = True
 
@@ -827,7 +848,7 @@ def main():
         return
 
     if args.config == "c5":
-        c5 = c5_leg(dist, dev, rank, world, args.steps, args.warmup)
+        c5 = c5_leg(dist, dev, rank, world, args.steps, args.warmup, args.dump_outputs)
         if rank == 0:
             ms = c5["compute_only"]["ms_per_step"]
             print(json.dumps({"metric": "effective TFLOPS (2*M*N*K), Q4_K mul_mat [32768x8192]x[8192x512] row-sharded", "value": c5["compute_only"]["tflops"], "unit": "TFLOP/s",
@@ -863,69 +884,74 @@ def main():
     flops_step = h.flops * world
     value = flops_step / (ms_per_step * 1e-3) / 1e12
 
-    # ---- the dominant kernel alone, HIP events on the launch stream.  Where the step is ONE launch (route 11) that launch IS the dominant kernel and its duration is the
-    # step's; the two launches it replaces (activation quantizer alone, GEMM alone on prepared activations) are timed beside it for the record
-    fused = args.variant == 0 and args.splitk == 0 and one_launch(Q4_K, M, K, B)
-    quant_us = events_us(h.prepare, args.steps, 10)
-    h.prepare()
-    gemm2_us = events_us(h.gemm_only, args.steps, 10)
-    gemm_us = events_us(h.step, args.steps, 10) if fused else gemm2_us
-    gemm_tf = h.flops / gemm_us / 1e6
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y" if world == 1 else "y_rank%d" % rank: h.y}, DUMP_BYTES // world)
     out = None
     if rank == 0:
-        # the same launches on all-zero operands: identical instruction stream and traffic, no toggling in the matrix pipe — the gap
-        # is what the chip's power management takes (a diagnostic beside the roofline fraction, not a result)
-        zero_us = None
-        try:
-            if args.lean:
-                raise RuntimeError("lean")
-            hz = Hot(dev, Q4_K, np.zeros_like(w), M, K, np.zeros_like(x), args.variant, args.splitk)
-            hz.ws.zero_()
-            zero_us = round(events_us(hz.step if fused else hz.gemm_only, 40, 10), 3)
-            del hz
-        except Exception:  # noqa: BLE001
-            pass
         out = {
             "metric": "effective TFLOPS (2*M*N*K), Q4_K mul_mat [4096x4096]x[4096x512]", "value": round(value, 3), "unit": "TFLOP/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 5),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic (%s)" % how,
             "config": {"workload": "Q4_K MUL_MAT [4096x4096]·[4096x512] per GPU; step = Q8_K activation quantize + fp16-MFMA GEMM, W and fp32 X resident in HBM",
                        "M_per_gpu": M, "K": K, "B": B, "parallelism": "row-split x%d, output left sharded" % world, "gemm_variant": args.variant, "splitk": args.splitk,
-                       "device_mode": "owned (GGML_CDNA4_OWNED_DEVICE=1: bench.py has the GPU to itself); the library's default is the shared mode — see roofline.step_us_default_shared_mode"},
+                       "device_mode": "owned (GGML_CDNA4_OWNED_DEVICE=1: bench.py has the GPU to itself); the library's default is the shared mode — see roofline.step_us_default_shared_mode (--full)"},
             "tokens_per_s": round(B * world / (ms_per_step * 1e-3), 1),
-            "roofline": {"bound": "mfma", "kernel": kernel_name(Q4_K, M, K, B, fused) if args.variant == 0 else "gemm variant %d" % args.variant,
-                         "achieved": round(gemm_tf, 3), "peak": MFMA_F16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(gemm_tf / MFMA_F16_PEAK_TFLOPS, 4),
-                         "traffic": pmc_traffic("k_gemm_kq_t64<12, 128, false, 0, false, true>" if fused else "k_gemm_kq_t64<12, 128, false, 0, false, false>") if args.variant == 0 else None,
-                         "traffic_note": "HBM-side bytes/launch (FETCH_SIZE x2 + WRITE_SIZE) from the rocprofv3 PMC passes of this command, profiles/rNN/pmc_summary.txt",
-                         "us_per_launch": round(gemm_us, 3), "algorithmic_flops_per_launch": h.flops, "us_per_launch_all_zero_operands": zero_us,
-                         # the whole step as the host loop times it (one launch, or quantizer + GEMM + the gap between them) against the same roof: value / peak
-                         "step_frac": round(value / world / MFMA_F16_PEAK_TFLOPS, 4),
-                         "launches_per_step": 1 if fused else 2,
-                         # the two launches the one-launch step replaces, each alone: the activation quantizer and the GEMM on prepared activations (AUTO's ticketed split)
-                         "two_launch_components_us": {"k_quantize_q8_K": round(quant_us, 3), "k_gemm_kq_t64<Q4_K, 128>": round(gemm2_us, 3)},
-                         # the in-graph case: the producer of src1 — the NORM chain's launch — already left the activation image, so the MUL_MAT node is the GEMM
-                         # alone on prepared activations (ggml_cdna4_mul_mat_prepared: what the plug-in issues for wq / wk / wv / w_gate / w_up behind a norm)
-                         "step_us_image_from_producer": round(gemm2_us, 3), "step_frac_image_from_producer": round(h.flops / gemm2_us / 1e6 / MFMA_F16_PEAK_TFLOPS, 4)},
         }
-        # the same step in the library's DEFAULT mode (shared device: quantizer launch + GEMM with the ticketed split — nothing waits for a co-resident work-group)
-        try:
-            L_ = native.lib(); old_mode = L_.ggml_cdna4_set_shared_device(1)
-            out["roofline"]["step_us_default_shared_mode"] = round(events_us(h.step, args.steps, 10), 3)
-            L_.ggml_cdna4_set_shared_device(old_mode)
-        except Exception as e:  # noqa: BLE001
-            out["roofline"]["step_us_default_shared_mode"] = repr(e)[:120]
-        # the step's other kernel, HBM-bound: reads the fp32 activations once, writes the pair-interleaved fp16 image + per-256 scale and per-16 sums
-        qbytes = B * K * 4 + B * K * 2 + B * (K // 256) * 4 + B * (K // 16) * 2
-        out["quantizer"] = {"kernel": "k_quantize_q8_K (fp32 rows -> fp16 GEMM image of the Q8_K-rounded activations, d, bsums)", "bound": "hbm", "us_per_launch": round(quant_us, 3),
-                            "algorithmic_bytes_per_launch": qbytes, "achieved": round(qbytes / quant_us / 1e3, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                            "frac": round(qbytes / quant_us / 1e3 / HBM_PEAK_GBS, 4)}
-        if world == 1 and not args.lean:
-            out["roofline"]["library_ceiling"] = library_ceiling(dev, M, K, B, args.steps)
-            lc = out["roofline"]["library_ceiling"]
-            if "tflops" in lc:
-                lc["ours_over_library"] = round(gemm_tf / lc["tflops"], 3)
 
-    if dist is not None:
+    if full:
+        # ---- the dominant kernel alone, HIP events on the launch stream.  Where the step is ONE launch (route 11) that launch IS the dominant kernel and its duration is the
+        # step's; the two launches it replaces (activation quantizer alone, GEMM alone on prepared activations) are timed beside it for the record
+        fused = args.variant == 0 and args.splitk == 0 and one_launch(Q4_K, M, K, B)
+        quant_us = events_us(h.prepare, args.steps, 10)
+        h.prepare()
+        gemm2_us = events_us(h.gemm_only, args.steps, 10)
+        gemm_us = events_us(h.step, args.steps, 10) if fused else gemm2_us
+        gemm_tf = h.flops / gemm_us / 1e6
+        if rank == 0:
+            # the same launches on all-zero operands: identical instruction stream and traffic, no toggling in the matrix pipe — the gap
+            # is what the chip's power management takes (a diagnostic beside the roofline fraction, not a result)
+            zero_us = None
+            try:
+                if args.lean:
+                    raise RuntimeError("lean")
+                hz = Hot(dev, Q4_K, np.zeros_like(w), M, K, np.zeros_like(x), args.variant, args.splitk)
+                hz.ws.zero_()
+                zero_us = round(events_us(hz.step if fused else hz.gemm_only, 40, 10), 3)
+                del hz
+            except Exception:  # noqa: BLE001
+                pass
+            out["roofline"] = {"bound": "mfma", "kernel": kernel_name(Q4_K, M, K, B, fused) if args.variant == 0 else "gemm variant %d" % args.variant,
+                               "achieved": round(gemm_tf, 3), "peak": MFMA_F16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(gemm_tf / MFMA_F16_PEAK_TFLOPS, 4),
+                               "traffic": pmc_traffic("k_gemm_kq_t64<12, 128, false, 0, false, true>" if fused else "k_gemm_kq_t64<12, 128, false, 0, false, false>") if args.variant == 0 else None,
+                               "traffic_note": "HBM-side bytes/launch (FETCH_SIZE x2 + WRITE_SIZE) from the rocprofv3 PMC passes of this command, profiles/rNN/pmc_summary.txt",
+                               "us_per_launch": round(gemm_us, 3), "algorithmic_flops_per_launch": h.flops, "us_per_launch_all_zero_operands": zero_us,
+                               # the whole step as the host loop times it (one launch, or quantizer + GEMM + the gap between them) against the same roof: value / peak
+                               "step_frac": round(value / world / MFMA_F16_PEAK_TFLOPS, 4),
+                               "launches_per_step": 1 if fused else 2,
+                               # the two launches the one-launch step replaces, each alone: the activation quantizer and the GEMM on prepared activations (AUTO's ticketed split)
+                               "two_launch_components_us": {"k_quantize_q8_K": round(quant_us, 3), "k_gemm_kq_t64<Q4_K, 128>": round(gemm2_us, 3)},
+                               # the in-graph case: the producer of src1 — the NORM chain's launch — already left the activation image, so the MUL_MAT node is the GEMM
+                               # alone on prepared activations (ggml_cdna4_mul_mat_prepared: what the plug-in issues for wq / wk / wv / w_gate / w_up behind a norm)
+                               "step_us_image_from_producer": round(gemm2_us, 3), "step_frac_image_from_producer": round(h.flops / gemm2_us / 1e6 / MFMA_F16_PEAK_TFLOPS, 4)}
+            # the same step in the library's DEFAULT mode (shared device: quantizer launch + GEMM with the ticketed split — nothing waits for a co-resident work-group)
+            try:
+                L_ = native.lib(); old_mode = L_.ggml_cdna4_set_shared_device(1)
+                out["roofline"]["step_us_default_shared_mode"] = round(events_us(h.step, args.steps, 10), 3)
+                L_.ggml_cdna4_set_shared_device(old_mode)
+            except Exception as e:  # noqa: BLE001
+                out["roofline"]["step_us_default_shared_mode"] = repr(e)[:120]
+            # the step's other kernel, HBM-bound: reads the fp32 activations once, writes the pair-interleaved fp16 image + per-256 scale and per-16 sums
+            qbytes = B * K * 4 + B * K * 2 + B * (K // 256) * 4 + B * (K // 16) * 2
+            out["quantizer"] = {"kernel": "k_quantize_q8_K (fp32 rows -> fp16 GEMM image of the Q8_K-rounded activations, d, bsums)", "bound": "hbm", "us_per_launch": round(quant_us, 3),
+                                "algorithmic_bytes_per_launch": qbytes, "achieved": round(qbytes / quant_us / 1e3, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": round(qbytes / quant_us / 1e3 / HBM_PEAK_GBS, 4)}
+            if world == 1 and not args.lean:
+                out["roofline"]["library_ceiling"] = library_ceiling(dev, M, K, B, args.steps)
+                lc = out["roofline"]["library_ceiling"]
+                if "tflops" in lc:
+                    lc["ours_over_library"] = round(gemm_tf / lc["tflops"], 3)
+
+    if dist is not None and full:
         # the headline's own collective legs (`value` is the compute-only weak-scaling number — the output of a row-split layer stays sharded, its
         # consumer reads its own shard — and a >= 6x there says nothing about xGMI): the same step followed by the RCCL all-gather of the output, fp32 and fp16
         legs = {"compute_only": {"ms_per_step": round(ms_per_step, 5), "tflops": round(value, 3)}}
@@ -942,14 +968,14 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             ms_c = float(tt.item()) / args.steps * 1e3
             legs[name] = {"ms_per_step": round(ms_c, 5), "tflops": round(flops_step / (ms_c * 1e-3) / 1e12, 3), "collective": "RCCL all_gather_into_tensor, %d B/rank" % nbytes}
-        c5 = c5_leg(dist, dev, rank, world, max(10, args.steps // 4), max(3, args.warmup // 4))      # a default multi-GPU run also carries BASELINE configs[4]
+        c5 = c5_leg(dist, dev, rank, world, max(10, args.steps // 4), max(3, args.warmup // 4))      # a --full multi-GPU run also carries BASELINE configs[4]
         if rank == 0:
             out["collective_legs"] = legs
             out["accounting"] = ("`value` = compute_only: weak scaling of the headline with the output left sharded (no collective in the timed region); collective_legs has the same step "
                                  "with the RCCL all-gather of the output behind it; c5 (BASELINE configs[4], strong scaling) carries compute_only / with_allgather_* / ksplit_allreduce")
             out["c5"] = c5
 
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and full:
         if not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(M, K, B)
         if extras:

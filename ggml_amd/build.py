@@ -3,10 +3,14 @@
   libcdna4_kernels.so   hand-written HIP kernels + the C-ABI of include/ggml_cdna4.h, and the GGUF reader of
                         include/ggml_cdna4_gguf.h (host code)                                 (always)
   libggml-cdna4.so      ggml backend plug-in (ggml_backend_init), compiled against the ggml headers of the
-                        reference tree where they lie — only when that tree is present; the prebuilt
-                        .so travels to the GPU box with the snapshot.
-Both land in ggml_amd/lib/ (git-ignored, in-tree so the GPU box sees them).
+                        reference tree where they lie — only when that tree is present.  A copy is kept
+                        in oracle/_ref/ beside the other binaries built from that tree, with the sha256 of
+                        the plug-in and C-ABI sources it was built from; on a machine without the tree,
+                        build() installs that copy if those sources are the ones in this tree.
+Both land in ggml_amd/lib/ (git-ignored).
 """
+import filecmp
+import hashlib
 import os
 import shutil
 import subprocess
@@ -77,14 +81,42 @@ def have_reference():
     return os.path.exists(os.path.join(REF, "src", "ggml-backend-impl.h"))
 
 
+def _digest(paths):
+    """sha256 over the repository-relative names and the contents of paths"""
+    h = hashlib.sha256()
+    for p in sorted(paths):
+        h.update(os.path.relpath(p, ROOT).encode() + b"\0")
+        with open(p, "rb") as f:
+            h.update(f.read())
+    return h.hexdigest()
+
+
 def build_backend(force=False, verbose=False):
-    """the ggml plug-in; needs the ggml headers (reference tree).  Returns the path or None."""
+    """the ggml plug-in; needs the ggml headers (reference tree).  A copy goes to oracle/_ref/, with the digest of the sources it was
+    built from; without the tree that copy is installed when these sources are the same.  Returns the path or None."""
     out = os.path.join(LIB, "libggml-cdna4.so")
+    kept = os.path.join(ROOT, "oracle", "_ref", "libggml-cdna4.so")
+    stamp = kept + ".sha256"
     srcs = [os.path.join(CSRC, s) for s in BACKEND_SRCS]
     if not all(os.path.exists(s) for s in srcs):
         return None
     if not have_reference():
-        return out if os.path.exists(out) else None
+        if not os.path.exists(kept):
+            return out if os.path.exists(out) else None
+        built_from = open(stamp).read().strip() if os.path.exists(stamp) else None
+        if built_from != _digest(srcs + _headers()):
+            # without the tree, ggml_amd/lib/ only ever holds an installed copy: one that does not match these sources goes too
+            if os.path.exists(out):
+                os.remove(out)
+            print("[build] oracle/_ref/libggml-cdna4.so was built from other plug-in / C-ABI sources than these: not installed "
+                  "(build() where the reference tree is makes a current one)", file=sys.stderr)
+            return None
+        if not (os.path.exists(out) and filecmp.cmp(kept, out, shallow=False)):
+            os.makedirs(LIB, exist_ok=True)
+            shutil.copy2(kept, out)
+            if verbose:
+                print("[build] installed the ggml backend plug-in from oracle/_ref", file=sys.stderr)
+        return out
     kern = os.path.join(LIB, "libcdna4_kernels.so")
     if force or _newer(srcs + _headers() + [kern], out):
         if verbose:
@@ -94,6 +126,12 @@ def build_backend(force=False, verbose=False):
                "-I" + os.path.join(REF, "include"), "-I" + os.path.join(REF, "src"), "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(CSRC, "backend"),
                "-o", out] + srcs + ["-L" + LIB, "-lcdna4_kernels", "-Wl,-rpath,$ORIGIN"]
         _run(cmd)
+    digest = _digest(srcs + _headers())
+    if _newer([out], kept) or not os.path.exists(stamp) or open(stamp).read().strip() != digest:
+        os.makedirs(os.path.dirname(kept), exist_ok=True)
+        shutil.copy2(out, kept)
+        with open(stamp, "w") as f:
+            f.write(digest + "\n")
     return out
 
 

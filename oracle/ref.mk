@@ -12,6 +12,8 @@
 #   oracle/_ref/gpt2_harness      (oracle/gpt2_harness.cpp: includes examples/gpt-2/main-backend.cpp verbatim)
 #   oracle/_ref/sched_harness     (oracle/sched_harness.cpp: includes examples/gpt-2/main-sched.cpp verbatim; ggml_backend_sched)
 #   oracle/_ref/split_harness     (oracle/split_harness.cpp: split buffer type, async copies, events, pinned host buffers via the public API)
+#   oracle/_ref/libggml-cdna4.so (+ .sha256)  not made by this recipe: ggml_amd/build.py puts a copy of the project's own plug-in here,
+#                                with the digest of its sources, for build() on machines without the reference tree to install
 #
 # ISA flags: x86-64-v3 (AVX2+FMA+F16C) instead of the reference's default -march=native so the same
 # binaries run on this container's Xeon and on the GPU box's host CPU.  That selects the AVX2 bodies

@@ -1,9 +1,11 @@
 #!/bin/bash
 # PMC passes over gemm_bench (product kernels): where do the waves of the t64 / w12 kernels spend their cycles?
-R="$(cd "$(dirname "$0")/.." && pwd)"; mkdir -p "$R/gpurun_out"; cd /tmp; export TMPDIR=/tmp
+R="$(cd "$(dirname "$0")/.." && pwd)"; cd "$R"
+OUT=$(mkdir -p "${CDNA4_OUT:-out}" && cd "${CDNA4_OUT:-out}" && pwd); export CDNA4_OUT="$OUT"      # all output of the session, the tests' reports included
+cd /tmp; export TMPDIR=/tmp
 run() { # name, pmc list, M K B variants splitk
   local name=$1 pmc=$2; shift 2
-  GB_ROUNDS=1 GB_VARIANTS="$4" GB_SPLITKS="$5" timeout -k 10 200 rocprofv3 --kernel-trace --pmc $pmc --output-format csv -d "$R/gpurun_out/pmcg_$name" -o p -- "$R/tools/microbench/gemm_bench" $1 $2 $3 "" > "$R/gpurun_out/pmcg_$name.log" 2>&1
+  GB_ROUNDS=1 GB_VARIANTS="$4" GB_SPLITKS="$5" timeout -k 10 200 rocprofv3 --kernel-trace --pmc $pmc --output-format csv -d "$OUT/pmcg_$name" -o p -- "$R/tools/microbench/gemm_bench" $1 $2 $3 "" > "$OUT/pmcg_$name.log" 2>&1
 }
 for shape in "c5 32768 8192 512 40967 1" "head 4096 4096 512 24583,4119 2"; do
   set -- $shape; tag=$1; shift
@@ -14,7 +16,7 @@ for shape in "c5 32768 8192 512 40967 1" "head 4096 4096 512 24583,4119 2"; do
 done
 cd "$R"; python3 - <<'PY'
 import csv, glob, collections, os
-for d in sorted(glob.glob('gpurun_out/pmcg_*')):
+for d in sorted(glob.glob(os.environ['CDNA4_OUT'] + '/pmcg_*')):
     f=os.path.join(d,'p_counter_collection.csv')
     if not os.path.isdir(d) or not os.path.exists(f): print(d,'no csv'); continue
     agg=collections.defaultdict(lambda: collections.defaultdict(list))

@@ -6,7 +6,7 @@ import torch
 import refutil as R
 from ggml_amd import ops
 
-REPORT = os.path.join(R.ROOT, "gpurun_out", "parity_report.jsonl")
+REPORT = os.path.join(R.OUT_DIR, "parity_report.jsonl")
 
 
 def report(**kw):

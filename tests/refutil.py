@@ -7,6 +7,14 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_SO = os.path.join(ROOT, "oracle", "libggml_oracle.so")
 REF_DIR = os.path.join(ROOT, "oracle", "_ref")
+# where the GPU tests leave their reports (parity figures, harness logs): the output folder of the scripts/ sessions
+OUT_DIR = os.environ.get("CDNA4_OUT") or os.path.join(ROOT, "out")
+
+
+def out_path(name):
+    """OUT_DIR/name, the folder created"""
+    os.makedirs(OUT_DIR, exist_ok=True)
+    return os.path.join(OUT_DIR, name)
 
 # ggml type ids (include/ggml.h:351-390)
 F32, F16, Q4_0, Q8_0, Q4_K, Q5_K, Q6_K, Q8_K = 0, 1, 2, 8, 12, 13, 14, 15

@@ -95,3 +95,17 @@ def test_gpus_n_without_a_launcher_spawns_n_ranks():
     r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2"], capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
     l1 = [json.loads(l) for l in r1.stdout.splitlines() if l.startswith("{")]
     assert r1.returncode == 0 and len(l1) == 1 and l1[0]["n_gpus"] == 1, (r1.stdout + r1.stderr)[-1000:]
+
+
+def test_dump_outputs_writes_float32_within_the_budget(tmp_path):
+    """--dump-outputs: DIR/<name>.npy in float32; an output above its share of the byte budget keeps every s-th column, a smaller one is whole"""
+    import torch
+    b = _bench()
+    y = torch.arange(6 * 40, dtype=torch.float64).reshape(6, 40)
+    budget = 800                                                        # 400 bytes a name: y (960 bytes in float32) keeps every 3rd column
+    b.dump_outputs(str(tmp_path), {"y": y, "small": y[:, :4]}, budget)
+    assert sorted(os.listdir(tmp_path)) == ["small.npy", "y.npy"]
+    a, s = np.load(tmp_path / "y.npy"), np.load(tmp_path / "small.npy")
+    assert a.dtype == np.float32 and s.dtype == np.float32
+    assert np.array_equal(a, y.numpy()[:, ::3].astype(np.float32)) and np.array_equal(s, y.numpy()[:, :4].astype(np.float32))
+    assert a.nbytes + s.nbytes <= budget

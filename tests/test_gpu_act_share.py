@@ -159,8 +159,7 @@ def _harness(type_, d, h, b, share, exact=False):
     j = json.loads(r.stdout.strip().splitlines()[-1])
     j["share"] = share
     j["exact"] = exact
-    os.makedirs(os.path.join(R.ROOT, "gpurun_out"), exist_ok=True)
-    with open(os.path.join(R.ROOT, "gpurun_out", "split_report.jsonl"), "a") as f:
+    with open(R.out_path("split_report.jsonl"), "a") as f:
         f.write(json.dumps(j) + "\n")
     return j
 
@@ -172,7 +171,7 @@ def test_a_layers_shared_activations_are_quantized_once_through_ggmls_public_api
     (K-quants: the Q8_K image; Q4_0 / Q8_0: the Q8_0 image), where the rms_norm chain's own launch leaves the image and wq / w_gate take the hand-off too (none at decode size, where the quantizer lives inside
     the GEMV launch).  THE GATE: the outputs' bytes equal those of a run with the hand-off off.  Against the CPU backend: K and V — one product of the norm's output — within north_star's
     per-product 1e-3.  `out` sits behind two RE-QUANTIZATIONS of computed activations, where a last-bit difference in Q moves int8 steps of the next product's input (the CPU algorithm's own
-    sensitivity to its inputs): its distance is REPORTED (gpurun_out/split_report.jsonl), not asserted — what is asserted for the chain is the reference-order run below, which is bit-identical."""
+    sensitivity to its inputs): its distance is REPORTED (split_report.jsonl in the output folder, refutil.OUT_DIR), not asserted — what is asserted for the chain is the reference-order run below, which is bit-identical."""
     on, off = _harness(type_, d, h, b, True), _harness(type_, d, h, b, False)
     assert on["act_hand_offs_first_compute"] == hand_offs and off["act_hand_offs_first_compute"] == 0, (on, off)
     assert on["fnv1a"] == off["fnv1a"], (on, off)
@@ -199,8 +198,7 @@ def _moeffn(type_, d, h, tokens, share):
     assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
     j = json.loads(r.stdout.strip().splitlines()[-1])
     j["share"] = share
-    os.makedirs(os.path.join(R.ROOT, "gpurun_out"), exist_ok=True)
-    with open(os.path.join(R.ROOT, "gpurun_out", "split_report.jsonl"), "a") as f:
+    with open(R.out_path("split_report.jsonl"), "a") as f:
         f.write(json.dumps(j) + "\n")
     return j
 

@@ -21,8 +21,7 @@ def _run(op):
     env = dict(os.environ, GGML_BACKEND_PATH=PLUGIN)
     r = subprocess.run([HARNESS, "test", "-o", op, "-b", "CDNA40"], env=env, capture_output=True, text=True, timeout=900)
     txt = re.sub(r"\x1b\[[0-9;]*m", "", r.stdout + r.stderr)
-    os.makedirs(os.path.join(R.ROOT, "gpurun_out"), exist_ok=True)
-    open(os.path.join(R.ROOT, "gpurun_out", "test-backend-ops_%s.log" % op), "w").write(txt)
+    open(R.out_path("test-backend-ops_%s.log" % op), "w").write(txt)
     return r.returncode, txt
 
 

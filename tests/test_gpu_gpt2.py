@@ -67,14 +67,14 @@ def test_gpt2_per_op_parity_on_identical_inputs(model, n_prompt):
     import re
     q4, _ = model
     out = _harness([q4, "CDNA40", PLUGIN, "RESYNC", n_prompt, 1, 16])
-    open(os.path.join(R.ROOT, "gpurun_out", "gpt2_resync_%d.log" % n_prompt), "w").write(out)
+    open(R.out_path("gpt2_resync_%d.log" % n_prompt), "w").write(out)
     rows = re.findall(r"node\s+(\d+)\s+(\S+)\s+.*?\[\s*(\d+),\s*(\d+),\s*(\d+)\] rel_l2=(\S+?)( NONFINITE-MISMATCH)?$", out, re.M)
     assert len(rows) > 300, out[-2000:]
     worst = {}
     for _, op, ne0, _, _, err, bad in rows:
         assert not bad, (op, err)
         worst[op] = max(worst.get(op, 0.0), float(err))
-    with open(os.path.join(R.ROOT, "gpurun_out", "gpt2_parity.jsonl"), "a") as f:
+    with open(R.out_path("gpt2_parity.jsonl"), "a") as f:
         f.write(json.dumps({"mode": "resync", "n_prompt": n_prompt, "worst_rel_l2_per_op": worst}) + "\n")
     for op, e in worst.items():
         assert e < (1e-3 if op == "MUL_MAT" else 1e-4), worst
@@ -88,8 +88,7 @@ def test_gpt2_logits_vs_cpu_backend(model, cpu_self_sensitivity, n_prompt, n_dec
     assert "CDNA4" in tg["backend"] and lc.shape == lg.shape == (1 + n_decode, N_VOCAB)
     errs = [R.rel_l2(lg[i], lc[i]) for i in range(lc.shape[0])]
     agree = [int(np.argmax(lg[i]) == np.argmax(lc[i])) for i in range(lc.shape[0])]
-    os.makedirs(os.path.join(R.ROOT, "gpurun_out"), exist_ok=True)
-    with open(os.path.join(R.ROOT, "gpurun_out", "gpt2_parity.jsonl"), "a") as f:
+    with open(R.out_path("gpt2_parity.jsonl"), "a") as f:
         f.write(json.dumps({"n_prompt": n_prompt, "n_decode": n_decode, "rel_l2_per_step": errs, "cpu_self_sensitivity_1e-6": cpu_self_sensitivity,
                             "cpu": tc, "gpu": tg, "argmax_agree": agree}) + "\n")
     assert np.isfinite(lg).all()
@@ -111,7 +110,7 @@ def test_gpt2_logits_vs_cpu_backend_reference_order_mode(model, n_prompt, n_deco
     assert "CDNA4" in tg["backend"] and lc.shape == lg.shape == (1 + n_decode, N_VOCAB)
     errs = [R.rel_l2(lg[i], lc[i]) for i in range(lc.shape[0])]
     ident = bool(np.array_equal(lg.view(np.uint32), lc.view(np.uint32)))
-    with open(os.path.join(R.ROOT, "gpurun_out", "gpt2_parity.jsonl"), "a") as f:
+    with open(R.out_path("gpt2_parity.jsonl"), "a") as f:
         f.write(json.dumps({"mode": "reference_order", "n_prompt": n_prompt, "n_decode": n_decode, "rel_l2_per_step": errs, "bit_identical": ident,
                             "cpu": tc, "gpu": tg}) + "\n")
     assert ident and max(errs) == 0.0, errs
@@ -125,14 +124,14 @@ def test_gpt2_per_op_parity_reference_order_mode_is_bit_exact(model):
     r = subprocess.run([os.path.join(REF, "gpt2_harness"), q4, "CDNA40", PLUGIN, "RESYNC", "8", "1", "16"], capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, GGML_CDNA4_EXACT="1"))
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
-    open(os.path.join(R.ROOT, "gpurun_out", "gpt2_resync_exact_8.log"), "w").write(r.stdout)
+    open(R.out_path("gpt2_resync_exact_8.log"), "w").write(r.stdout)
     rows = re.findall(r"node\s+(\d+)\s+(\S+)\s+.*?\[\s*(\d+),\s*(\d+),\s*(\d+)\] rel_l2=(\S+?)( NONFINITE-MISMATCH)?$", r.stdout, re.M)
     assert len(rows) > 300, r.stdout[-2000:]
     worst = {}
     for _, op, _, _, _, err, bad in rows:
         assert not bad, (op, err)
         worst[op] = max(worst.get(op, 0.0), float(err))
-    with open(os.path.join(R.ROOT, "gpurun_out", "gpt2_parity.jsonl"), "a") as f:
+    with open(R.out_path("gpt2_parity.jsonl"), "a") as f:
         f.write(json.dumps({"mode": "resync_reference_order", "n_prompt": 8, "worst_rel_l2_per_op": worst}) + "\n")
     assert all(e == 0.0 for e in worst.values()), worst
 
@@ -145,7 +144,7 @@ def test_gpt2_graph_peepholes_change_no_bit_and_cut_the_launches(model):
     q4, d = model
     tf, lf = _run(q4, "CDNA40", os.path.join(d, "fused.bin"), 40, 48)
     tu, lu = _run(q4, "CDNA40", os.path.join(d, "unfused.bin"), 40, 48, env={"GGML_CDNA4_NO_FUSE": "1"})
-    with open(os.path.join(R.ROOT, "gpurun_out", "gpt2_parity.jsonl"), "a") as f:
+    with open(R.out_path("gpt2_parity.jsonl"), "a") as f:
         f.write(json.dumps({"mode": "peepholes", "fused": tf, "unfused": tu, "bit_identical": bool(np.array_equal(lf.view(np.uint32), lu.view(np.uint32)))}) + "\n")
     assert np.array_equal(lf.view(np.uint32), lu.view(np.uint32))
     assert tf["decode_ms_per_token"] < tu["decode_ms_per_token"]
@@ -176,7 +175,7 @@ def test_gpt2_logits_against_an_fp64_forward(tmp_path, seed):
         ex = GX.forward(hp, T, toks[:n_prompt + i])
         rows.append({"step": i, "gpu_vs_exact": R.rel_l2(lg[i], ex), "cpu_vs_exact": R.rel_l2(lc[i], ex), "gpu_vs_cpu": R.rel_l2(lg[i], lc[i]),
                      "logit_std": float(ex.std()), "argmax": [int(np.argmax(ex)), int(np.argmax(lg[i])), int(np.argmax(lc[i]))]})
-    with open(os.path.join(R.ROOT, "gpurun_out", "gpt2_parity.jsonl"), "a") as f:
+    with open(R.out_path("gpt2_parity.jsonl"), "a") as f:
         f.write(json.dumps({"mode": "fp64_exact", "seed": seed, "wte_std": 0.08, "n_prompt": n_prompt, "steps": rows}) + "\n")
     for r in rows:
         assert r["logit_std"] > 0.5
@@ -205,7 +204,7 @@ def test_gpt2_sched_graph_runs_unmodified(model, cpu_self_sensitivity, ngl, para
     assert "CDNA4" in tg["backends"] and "CDNA4" not in tc["backends"]
     assert lc.shape == lg.shape == (4, N_VOCAB) and np.isfinite(lg).all()
     errs = [R.rel_l2(lg[i], lc[i]) for i in range(4)]
-    with open(os.path.join(R.ROOT, "gpurun_out", "gpt2_parity.jsonl"), "a") as f:
+    with open(R.out_path("gpt2_parity.jsonl"), "a") as f:
         f.write(json.dumps({"mode": "sched", "rel_l2_per_step": errs, "cpu": tc, "gpu": tg, "cpu_self_sensitivity_1e-6": cpu_self_sensitivity}) + "\n")
     assert max(errs) < 1.25 * 1.63e-2 + 1e-3, (errs, cpu_self_sensitivity)          # 1.25 x measured (round 3) + 1e-3
     if ngl == 6:
@@ -232,5 +231,5 @@ def test_gpt2_from_gguf_equals_gpt2_from_bin(model):
     assert m, r.stderr[-1500:]
     rec = json.loads(m.group(0))
     assert "pinned staging" in rec["path"]
-    with open(os.path.join(R.ROOT, "gpurun_out", "gpt2_parity.jsonl"), "a") as f:
+    with open(R.out_path("gpt2_parity.jsonl"), "a") as f:
         f.write(json.dumps(dict(rec, mode="gguf_vs_bin", identical=True)) + "\n")

@@ -253,8 +253,7 @@ def test_resident_buffer_type_through_ggmls_public_api(type_, m, k, b):
     r = subprocess.run([EXE, PLUGIN, type_, str(m), str(k), str(b), "resident"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
     j = json.loads(r.stdout.strip().splitlines()[-1])
-    os.makedirs(os.path.join(R.ROOT, "gpurun_out"), exist_ok=True)
-    with open(os.path.join(R.ROOT, "gpurun_out", "split_report.jsonl"), "a") as f:
+    with open(R.out_path("split_report.jsonl"), "a") as f:
         f.write(json.dumps(j) + "\n")
     assert j["buft"].startswith("CDNA4_Resident")
     assert j["set_get_roundtrip"] is True
@@ -275,8 +274,7 @@ def test_expert_stack_in_the_resident_buffer_type_through_ggmls_public_api(type_
     r = subprocess.run([EXE, PLUGIN, type_, str(m), str(k), str(tokens), "moe"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
     j = json.loads(r.stdout.strip().splitlines()[-1])
-    os.makedirs(os.path.join(R.ROOT, "gpurun_out"), exist_ok=True)
-    with open(os.path.join(R.ROOT, "gpurun_out", "split_report.jsonl"), "a") as f:
+    with open(R.out_path("split_report.jsonl"), "a") as f:
         f.write(json.dumps(j) + "\n")
     assert j["resident_vs_cpu_rel_l2"] < 1e-3 and j["default_vs_cpu_rel_l2"] < 1e-3 and j["resident_vs_default_rel_l2"] < 1e-5, j
     assert j["resident_bit_identical_to_default"] is (not other_kernel), j
@@ -314,7 +312,7 @@ def test_buffer_from_host_ptr_through_ggmls_public_api(type_, m, k, b):
     r = subprocess.run([EXE, PLUGIN, type_, str(m), str(k), str(b), "hostptr"], capture_output=True, text=True, timeout=600, env=dict(os.environ, GGML_CDNA4_HOST_PTR_BUFFERS="1"))
     assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
     j = json.loads(r.stdout.strip().splitlines()[-1])
-    with open(os.path.join(R.ROOT, "gpurun_out", "split_report.jsonl"), "a") as f:
+    with open(R.out_path("split_report.jsonl"), "a") as f:
         f.write(json.dumps(j) + "\n")
     assert j["caps_buffer_from_host_ptr"] is True
     if type_ == "q8_0":                                                 # without the opt-in the device does not advertise it

@@ -30,8 +30,7 @@ def _run(type_, m, k, b, shards):
     import re
     j["graph_captures_replays"] = [[int(a), int(b)] for a, b in re.findall(r"(\d+) HIP-graph captures, (\d+) replays", r.stderr)]
     j["ksplit_rccl_sums"] = [[int(a), int(b)] for a, b in re.findall(r"K-split MUL_MAT: (\d+) RCCL all-reduces, (\d+) in-order sums", r.stderr)]
-    os.makedirs(os.path.join(R.ROOT, "gpurun_out"), exist_ok=True)
-    with open(os.path.join(R.ROOT, "gpurun_out", "split_report.jsonl"), "a") as f:
+    with open(R.out_path("split_report.jsonl"), "a") as f:
         f.write(json.dumps(dict(j, shards=shards)) + "\n")
     return j
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Condenses a gpurun_out/ directory written by scripts/gpu_full.sh into the small text/CSV files kept under
+"""Condenses the output folder of scripts/gpu_full.sh ($CDNA4_OUT) into the small text/CSV files kept under
 profiles/rNN/: rocprofv3 per-kernel stats, per-kernel averages of each PMC pass (with the gfx950 FETCH_SIZE x2
 correction of MI355X_MICROARCH.md §HBM spelled out), the bench line, parity summaries."""
 import collections
