@@ -250,13 +250,6 @@ static bool use_mmq(int type, int64_t M, int64_t K, int64_t B) {
     if (B >= 49) return M * K <= ((int64_t)1 << 24) || type == CDNA4_Q8_0 || type == CDNA4_Q5_K;
     return false;
 }
-static int resolve_path(int type, int path, int64_t M, int64_t K, int64_t B) {
-    if (path == GGML_CDNA4_PATH_AUTO) {
-        if (use_mmq(type, M, K, B)) return GGML_CDNA4_PATH_GEMV;
-        return (B > 8 && cdna4_gemm_q_supported(type, M, K, B)) ? GGML_CDNA4_PATH_GEMM : GGML_CDNA4_PATH_GEMV;
-    }
-    return path;
-}
 
 int ggml_cdna4_prepare_act(int type, const float *X, int64_t x_row_stride, int64_t K, int64_t B, void *workspace, size_t workspace_bytes, int path, void *stream) {
     if (!is_q(type)) return cdna4_set_error_msg("prepare_act: unsupported weight type");
@@ -289,179 +282,188 @@ static cdna4_gemm_args gemm_args_of(int type, const void *W, int64_t w_row_bytes
     a.Y = Y; a.y_row_elems = y_row_stride; a.M = (int)M; a.K = (int)K; a.B = (int)B; a.variant = gemm_variant; a.splitk = splitk; a.epi = epi;
     return a;
 }
-// epi: the MUL_MAT's tail; *tail_done says whether the launch applied it (GEMM route on k_gemm_kq_t64) — otherwise the caller appends k_epilogue
-static int mul_mat_prepared_impl(int type, const void *W, int64_t w_row_bytes, float *Y, int64_t y_row_stride, int64_t M, int64_t K, int64_t B,
-                                 const void *workspace, size_t workspace_bytes, int path, int gemm_variant, int splitk, const cdna4_epilogue &epi, bool *tail_done, void *stream);
-int ggml_cdna4_mul_mat_prepared(int type, const void *W, int64_t w_row_bytes, float *Y, int64_t y_row_stride, int64_t M, int64_t K, int64_t B,
-                                const void *workspace, size_t workspace_bytes, int path, int gemm_variant, int splitk, void *stream) {
-    if (const int frc = fault_status()) return frc;
-    bool done = false;
-    return mul_mat_prepared_impl(type, W, w_row_bytes, Y, y_row_stride, M, K, B, workspace, workspace_bytes, path, gemm_variant, splitk, cdna4_epilogue{}, &done, stream);
-}
-static int mul_mat_prepared_impl(int type, const void *W, int64_t w_row_bytes, float *Y, int64_t y_row_stride, int64_t M, int64_t K, int64_t B,
-                                 const void *workspace, size_t workspace_bytes, int path, int gemm_variant, int splitk, const cdna4_epilogue &epi, bool *tail_done, void *stream) {
-    *tail_done = false;
-    if (!is_q(type)) return cdna4_set_error_msg("mul_mat: unsupported weight type");
-    if (M <= 0 || B <= 0) return 0;
-    if (K <= 0 || ggml_cdna4_row_size(type, K) == 0) return cdna4_set_error_msg("mul_mat: K is not a whole number of blocks");
-    const ws_view v = carve(type, K, B, (void *)workspace);
-    if (workspace_bytes < v.total) return cdna4_set_error_msg("mul_mat: workspace too small");
-    const bool mmq = path == GGML_CDNA4_PATH_AUTO && use_mmq(type, M, K, B) && !(((uintptr_t)W | (uintptr_t)w_row_bytes) & (type == CDNA4_Q6_K ? 1 : 15));
-    path = resolve_path(type, path, M, K, B);
-    if (path == GGML_CDNA4_PATH_GEMM) {
-        cdna4_gemm_args a = gemm_args_of(type, W, w_row_bytes, v.xh, Y, y_row_stride, M, K, B, gemm_variant, splitk, epi);
-        *tail_done = cdna4_gemm_q_fuses_tail(a);                     // (the routing itself, probed: gemm_q_mfma.hip)
-        if (!*tail_done) a.epi = cdna4_epilogue{};                      // this route stores the plain product: the caller appends k_epilogue
-        return cdna4_launch_gemm_q(a, (hipStream_t)stream);
-    }
+// v: the quantized activations (ws_view{}: the kernel quantizes them itself); the MUL_MAT_ID callers add their ids with gemv_ids()
+static cdna4_gemv_args gemv_args_of(int type, const void *W, int64_t w_row_bytes, const ws_view &v, float *Y, int64_t y_col_stride, int64_t M, int64_t K, int64_t ncol,
+                                    const cdna4_epilogue &epi) {
     cdna4_gemv_args g{};
     g.type = type; g.W = (const uint8_t *)W; g.w_row_bytes = w_row_bytes; g.qs = v.qs; g.d = v.d; g.bsums = v.bsums;
-    g.Y = Y; g.y_col_stride = y_row_stride; g.M = (int)M; g.K = (int)K; g.ncol = (int)B; g.ids = nullptr; g.epi = epi;
-    *tail_done = true;
-    if (mmq) return cdna4_launch_mmq(g, (hipStream_t)stream);
-    return cdna4_launch_gemv_q(g, (hipStream_t)stream);
+    g.Y = Y; g.y_col_stride = y_col_stride; g.M = (int)M; g.K = (int)K; g.ncol = (int)ncol; g.epi = epi;
+    return g;
 }
 
+// ---- The routing plan of a MUL_MAT: the ONE place that decides which kernel a call takes.  The calls launch what it says,
+// the queries (route, image key, may_alias, the grouped call's admission) read its fields: change the routing here and nowhere else.
+enum mm_kind {
+    MM_NONE,            // not a supported call
+    MM_REENCODE,        // an exact re-encoding of the weights (convert_w.hip), then the plan of `reencode_target`
+    MM_GEMV_1,          // ONE launch: the activation quantizer inside the GEMV (workspace untouched)
+    MM_GEMV_STAGED,     // quantize + GEMV with the columns staged in LDS
+    MM_GEMV,            // quantize + k_gemv_q
+    MM_MMQ,             // quantize + the int8 matrix-core kernel (mmq_i8.hip)
+    MM_GEMM_1,          // ONE launch: the quantizer inside k_gemm_kq_t64 (which writes the image itself)
+    MM_GEMM,            // quantize + the fp16 MFMA GEMM
+};
+struct mm_plan {
+    mm_kind kind;
+    int route_id;           // what ggml_cdna4_mul_mat_route documents
+    uint32_t image_key;     // what ggml_cdna4_act_image_key documents
+    bool tail_in_store;     // the launch applies the epilogue itself (otherwise k_epilogue follows it)
+    int reencode_target;    // MM_REENCODE only, else -1
+};
+// Side-effect free.  X == nullptr: the image is already in the workspace (the `prepared` calls) — no re-encoding, no one-launch form, and the
+// GEMV path launches the plain k_gemv_q, never the staged form.  An explicit PATH_GEMV keeps the v_dot4 units (tests compare the two).
+static mm_plan plan_mul_mat(int type, const void *W, int64_t w_row_bytes, const float *X, int64_t x_row_stride, int64_t M, int64_t K, int64_t B,
+                            int path, int gemm_variant, int splitk, const void *workspace) {
+    mm_plan p = {MM_NONE, 0, 0, true, -1};
+    if (!is_q(type) || M <= 0 || B <= 0 || K <= 0 || ggml_cdna4_row_size(type, K) == 0) return p;
+    const bool autop = path == GGML_CDNA4_PATH_AUTO;
+    // Formats with an exact same-shape re-encoding (Q5_0 / IQ4_NL -> Q8_0, Q3_K -> Q6_K) follow their TARGET format onto the int8 matrix-core kernel
+    // where that one is chosen: its integer dots on Q8_0 activations are the CPU's own arithmetic for the source format (tests/test_gpu_widening.py).
+    // From 9 rows up: below that the re-encoding pass (~2.5x the weight bytes) costs more than the staged GEMV it would replace.
+    // The re-encoded rows are 16-byte aligned (library scratch, or a resident image).
+    const int kmul = cdna4_convert_weights_kmul(type), tgt = cdna4_convert_weights_target(type);
+    if (autop && X && kmul == 1 && tgt >= 0 && tgt != type && B >= 9 && use_mmq(tgt, M, K, B)) {
+        p = plan_mul_mat(tgt, (const void *)(uintptr_t)256, (int64_t)ggml_cdna4_row_size(tgt, K), X, x_row_stride, M, K, B,
+                         path, gemm_variant, splitk, workspace);
+        p.kind = MM_REENCODE; p.route_id += 100; p.image_key = 0; p.reencode_target = tgt;       // (the image is the TARGET format's)
+        return p;
+    }
+    const bool few = autop && use_mmq(type, M, K, B);                     // a batch size at which the int8 matrix cores win
+    bool gemm = path == GGML_CDNA4_PATH_GEMM || (autop && !few && B > 8);
+    if (gemm && !cdna4_gemm_q_supported(type, M, K, B)) {
+        if (!autop) return p;
+        gemm = false;
+    }
+    const uint32_t key = 1u | (is_kq(type) ? 2u : 0u) | (cdna4_is_q81(type) ? 4u : 0u) | (kmul == 2 ? 8u : 0u);
+    if (!gemm) {                                                          // the integer-dot family: the tail rides in the store
+        // one launch while the redundant per-work-group quantization is cheap: B x K up to 32 K values, B rounded to the instantiated 2 / 4 / 8 columns
+        const int64_t nbt = B <= 1 ? 1 : (B <= 2 ? 2 : (B <= 4 ? 4 : 8));
+        const bool w_ok = !(((uintptr_t)W | (uintptr_t)w_row_bytes) & (type == CDNA4_Q6_K ? 1 : 15));
+        const bool x_ok = X && !(((uintptr_t)X | (uintptr_t)(B > 1 ? x_row_stride * 4 : 0)) & 15);
+        if (few && w_ok) { p.kind = MM_MMQ; p.route_id = 3; p.image_key = key; }
+        else if (x_ok && cdna4_gemv_fused_supported(type, K, B) && (B == 1 || nbt * K <= 32768)) { p.kind = MM_GEMV_1; p.route_id = 1; }
+        else { p.kind = X && cdna4_gemv_staged_supported(type, K, B) ? MM_GEMV_STAGED : MM_GEMV; p.route_id = 2; }
+        return p;
+    }
+    // the GEMM side's single source of truth is its launcher, run with a probe armed (gemm_q_mfma.hip): it sees W's alignment and resident image, the
+    // image's alignment and, where the call hands its fp32 rows over next to a usable workspace, whether ONE launch does the whole step
+    const void *xh = carve(type, K, B, (void *)workspace).xh;
+    cdna4_gemm_args a = gemm_args_of(type, W, w_row_bytes, xh, nullptr, 0, M, K, B, gemm_variant, splitk, cdna4_epilogue{});
+    if (X && workspace && !((uintptr_t)workspace & 255)) { a.xf = X; a.xf_row_elems = x_row_stride; }
+    p.kind = cdna4_gemm_q_fuses_quantizer(a) ? MM_GEMM_1 : MM_GEMM;
+    p.route_id = cdna4_gemm_q_route(a); p.image_key = key | 16u; p.tail_in_store = cdna4_gemm_q_fuses_tail(a);
+    return p;
+}
+// the plan of the AUTO call on contiguous, 256-byte-aligned activations and workspace: what the queries answer from
+static mm_plan plan_query(int type, const void *W, int64_t w_row_bytes, int64_t M, int64_t K, int64_t B) {
+    return plan_mul_mat(type, W, w_row_bytes, (const float *)(uintptr_t)256, K, M, K, B, GGML_CDNA4_PATH_AUTO, 0, 0, (const void *)(uintptr_t)256);
+}
+static mm_plan plan_query(int type, int64_t M, int64_t K, int64_t B) {      // shape only: an aligned stand-in for W, contiguous rows
+    return plan_query(type, (const void *)(uintptr_t)256, (int64_t)ggml_cdna4_row_size(type, K), M, K, B);
+}
+
+// X == nullptr: the `prepared` twins (the image is in the workspace).  epi: the MUL_MAT's tail
 static int mul_mat_impl(int type, const void *W, int64_t w_row_bytes, const float *X, int64_t x_row_stride, float *Y, int64_t y_row_stride,
-                        int64_t M, int64_t K, int64_t B, void *workspace, size_t workspace_bytes, int path, int gemm_variant, int splitk, const cdna4_epilogue &epi, void *stream) {
+                        int64_t M, int64_t K, int64_t B, void *workspace, size_t workspace_bytes, int path, int gemm_variant, int splitk,
+                        const cdna4_epilogue &epi, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (!is_q(type)) return cdna4_set_error_msg("mul_mat: unsupported weight type");
     if (M <= 0 || B <= 0) return 0;
     if (K <= 0 || ggml_cdna4_row_size(type, K) == 0) return cdna4_set_error_msg("mul_mat: K is not a whole number of blocks");
-    // Formats that reach the MFMA kernels through an exact re-encoding (Q5_0 / IQ4_NL -> Q8_0, convert_w.hip) follow their TARGET format onto the int8
-    // matrix-core kernel at the batch sizes where that one is chosen: re-encode into scratch, then the target's route (its integer dots on Q8_0
-    // activations are the CPU's own arithmetic for the source format: vec_dot_q5_0_q8_0 / vec_dot_iq4_nl_q8_0 on the same quants).  Same result as
-    // ggml_cdna4_convert_weights up front + ggml_cdna4_mul_mat on the target format (tests/test_gpu_widening.py).
-    if (path == GGML_CDNA4_PATH_AUTO && cdna4_convert_weights_kmul(type) == 1) {
-        const int tgt = cdna4_convert_weights_target(type);
-        // (from 9 rows up: below that the re-encoding pass — ~2.5x the weight bytes — costs more than the staged GEMV it would replace)
-        if (tgt >= 0 && tgt != type && B >= 9 && use_mmq(tgt, M, K, B)) {
-            uint8_t *cw = const_cast<uint8_t *>(cdna4_resident_lookup(type, W, w_row_bytes, M, K));      // a resident image (built once at load): no conversion launch
-            if (!cw) {
-                cw = (uint8_t *)cdna4_gemm_scratch(cdna4_convert_weights_bytes(type, M, K) + 256, 3);
-                if (!cw) return cdna4_set_error_msg("mul_mat: cannot allocate the re-encoded weights");
-                const int rc = cdna4_launch_convert_weights(type, (const uint8_t *)W, w_row_bytes, M, K, cw, (hipStream_t)stream);
-                if (rc) return rc;
-            }
-            return mul_mat_impl(tgt, cw, (int64_t)ggml_cdna4_row_size(tgt, K), X, x_row_stride, Y, y_row_stride, M, K, B, workspace, workspace_bytes, path, gemm_variant, splitk, epi, stream);
+    const mm_plan p = plan_mul_mat(type, W, w_row_bytes, X, x_row_stride, M, K, B, path, gemm_variant, splitk, workspace);
+    if (p.kind == MM_NONE) return cdna4_set_error_msg("mul_mat: GEMM path does not support this shape");
+    if (p.kind == MM_REENCODE) {
+        // re-encode into scratch, then the target's own call: the same result as ggml_cdna4_convert_weights up front + ggml_cdna4_mul_mat on the target
+        const int tgt = p.reencode_target;
+        uint8_t *cw = const_cast<uint8_t *>(cdna4_resident_lookup(type, W, w_row_bytes, M, K));      // a resident image: no conversion launch
+        if (!cw) {
+            cw = (uint8_t *)cdna4_gemm_scratch(cdna4_convert_weights_bytes(type, M, K) + 256, 3);
+            if (!cw) return cdna4_set_error_msg("mul_mat: cannot allocate the re-encoded weights");
+            if (const int rc = cdna4_launch_convert_weights(type, (const uint8_t *)W, w_row_bytes, M, K, cw, st)) return rc;
         }
+        return mul_mat_impl(tgt, cw, (int64_t)ggml_cdna4_row_size(tgt, K), X, x_row_stride, Y, y_row_stride, M, K, B, workspace, workspace_bytes,
+                            path, gemm_variant, splitk, epi, stream);
     }
-    // the int8 matrix-core kernel: AUTO only (an explicit PATH_GEMV keeps the v_dot4 units — tests compare the two), aligned Q4_K rows
-    const bool mmq = path == GGML_CDNA4_PATH_AUTO && use_mmq(type, M, K, B) && !(((uintptr_t)W | (uintptr_t)w_row_bytes) & (type == CDNA4_Q6_K ? 1 : 15));
-    path = resolve_path(type, path, M, K, B);
-    if (path == GGML_CDNA4_PATH_GEMM && !cdna4_gemm_q_supported(type, M, K, B)) return cdna4_set_error_msg("mul_mat: GEMM path does not support this shape");
-    // one launch while the redundant per-work-group quantization is cheap (B x K up to 32 K values, rounded to the instantiated 2 / 4 / 8 columns)
-    const int64_t nbt = B <= 1 ? 1 : (B <= 2 ? 2 : (B <= 4 ? 4 : 8));
-    if (!mmq && path == GGML_CDNA4_PATH_GEMV && cdna4_gemv_fused_supported(type, K, B) && (B == 1 || nbt * K <= 32768) && !(((uintptr_t)X | (uintptr_t)(B > 1 ? x_row_stride * 4 : 0)) & 15)) {
-        // decode with 1..8 activation rows: the activation quantizer runs inside the GEMV kernel (workspace untouched), ONE launch
-        cdna4_gemv_args g{};
-        g.type = type; g.W = (const uint8_t *)W; g.w_row_bytes = w_row_bytes; g.Y = Y; g.y_col_stride = y_row_stride;
-        g.M = (int)M; g.K = (int)K; g.ncol = (int)B; g.ids = nullptr; g.epi = epi;
-        return B == 1 ? cdna4_launch_gemv_q_fused(g, X, (hipStream_t)stream) : cdna4_launch_gemv_q_fused_n(g, X, x_row_stride, (hipStream_t)stream);
+    if (p.kind == MM_GEMV_1) {                                            // decode with 1..8 activation rows
+        const cdna4_gemv_args g = gemv_args_of(type, W, w_row_bytes, ws_view{}, Y, y_row_stride, M, K, B, epi);
+        return B == 1 ? cdna4_launch_gemv_q_fused(g, X, st) : cdna4_launch_gemv_q_fused_n(g, X, x_row_stride, st);
     }
-    if (path == GGML_CDNA4_PATH_GEMM && workspace && !((uintptr_t)workspace & 255)) {
-        // ONE launch for the whole step where the routing says so (k_gemm_kq_t64<.., FQ>: every work-group quantizes its share of X into the image in the workspace,
-        // a grid barrier, then the multiply — what ggml_compute_forward_mul_mat does inside one op, ggml-cpu.c:7490-7509 + :7428-7605); same sums, same order as the
-        // two launches below.  The routing code itself answers (probed: no side effects).
-        const ws_view v = carve(type, K, B, workspace);
+    const ws_view v = carve(type, K, B, workspace);
+    if (!X || p.kind == MM_GEMM_1) {                                      // nothing to quantize in front of the launch
         if (workspace_bytes < v.total) return cdna4_set_error_msg("mul_mat: workspace too small");
-        cdna4_gemm_args a = gemm_args_of(type, W, w_row_bytes, v.xh, Y, y_row_stride, M, K, B, gemm_variant, splitk, epi);
-        a.xf = X; a.xf_row_elems = x_row_stride;
-        if (cdna4_gemm_q_fuses_quantizer(a)) {
-            const bool tail_done = cdna4_gemm_q_fuses_tail(a);
-            if (!tail_done) a.epi = cdna4_epilogue{};
-            const int rc1 = cdna4_launch_gemm_q(a, (hipStream_t)stream);
-            if (rc1 || tail_done) return rc1;
-            return cdna4_launch_epilogue(Y, y_row_stride, M, B, epi, (hipStream_t)stream);
-        }
+    } else if (const int rc = ggml_cdna4_prepare_act(type, X, x_row_stride, K, B, workspace, workspace_bytes,
+                                                     p.kind == MM_GEMM ? GGML_CDNA4_PATH_GEMM : GGML_CDNA4_PATH_GEMV, stream)) return rc;
+    if (p.kind == MM_GEMM || p.kind == MM_GEMM_1) {
+        cdna4_gemm_args a = gemm_args_of(type, W, w_row_bytes, v.xh, Y, y_row_stride, M, K, B, gemm_variant, splitk,
+                                         p.tail_in_store ? epi : cdna4_epilogue{});
+        // MM_GEMM_1: k_gemm_kq_t64<.., FQ> — every work-group quantizes its share of X into the image, a grid barrier, then the multiply (what
+        // ggml_compute_forward_mul_mat does inside one op, ggml-cpu.c:7490-7509 + :7428-7605); same sums, same order as the two launches of MM_GEMM
+        if (p.kind == MM_GEMM_1) { a.xf = X; a.xf_row_elems = x_row_stride; }
+        const int rc = cdna4_launch_gemm_q(a, st);
+        if (rc || p.tail_in_store) return rc;
+        return cdna4_launch_epilogue(Y, y_row_stride, M, B, epi, st);      // the older GEMM kernels: one element-wise launch for the whole tail
     }
-    int rc = ggml_cdna4_prepare_act(type, X, x_row_stride, K, B, workspace, workspace_bytes, path, stream);
-    if (rc) return rc;
-    if (path == GGML_CDNA4_PATH_GEMV) {                                  // a few activation rows: the tail rides in the GEMV's store
-        const ws_view v = carve(type, K, B, workspace);
-        cdna4_gemv_args g{};
-        g.type = type; g.W = (const uint8_t *)W; g.w_row_bytes = w_row_bytes; g.qs = v.qs; g.d = v.d; g.bsums = v.bsums;
-        g.Y = Y; g.y_col_stride = y_row_stride; g.M = (int)M; g.K = (int)K; g.ncol = (int)B; g.ids = nullptr; g.epi = epi;
-        if (mmq) return cdna4_launch_mmq(g, (hipStream_t)stream);                                                   // 2..64 rows: int8 MFMA
-        if (cdna4_gemv_staged_supported(type, K, B)) return cdna4_launch_gemv_q_staged(g, (hipStream_t)stream);    // 2..8 rows: columns from LDS
-        return cdna4_launch_gemv_q(g, (hipStream_t)stream);
-    }
-    bool tail_done = false;
-    rc = mul_mat_prepared_impl(type, W, w_row_bytes, Y, y_row_stride, M, K, B, workspace, workspace_bytes, path, gemm_variant, splitk, epi, &tail_done, stream);
-    if (rc || tail_done) return rc;                                      // Q4_K: the tail went out with k_gemm_kq_t64's store
-    return cdna4_launch_epilogue(Y, y_row_stride, M, B, epi, (hipStream_t)stream);       // the older GEMM kernels: one element-wise launch for the whole tail
+    const cdna4_gemv_args g = gemv_args_of(type, W, w_row_bytes, v, Y, y_row_stride, M, K, B, epi);
+    if (p.kind == MM_MMQ) return cdna4_launch_mmq(g, st);                                 // 2..64 rows: int8 MFMA
+    if (p.kind == MM_GEMV_STAGED) return cdna4_launch_gemv_q_staged(g, st);               // 2..8 rows: columns from LDS
+    return cdna4_launch_gemv_q(g, st);
 }
 int ggml_cdna4_mul_mat(int type, const void *W, int64_t w_row_bytes, const float *X, int64_t x_row_stride, float *Y, int64_t y_row_stride,
                        int64_t M, int64_t K, int64_t B, void *workspace, size_t workspace_bytes, int path, int gemm_variant, int splitk, void *stream) {
     if (const int frc = fault_status()) return frc;
-    return mul_mat_impl(type, W, w_row_bytes, X, x_row_stride, Y, y_row_stride, M, K, B, workspace, workspace_bytes, path, gemm_variant, splitk, cdna4_epilogue{}, stream);
+    return mul_mat_impl(type, W, w_row_bytes, X, x_row_stride, Y, y_row_stride, M, K, B, workspace, workspace_bytes, path, gemm_variant, splitk,
+                        cdna4_epilogue{}, stream);
+}
+int ggml_cdna4_mul_mat_prepared(int type, const void *W, int64_t w_row_bytes, float *Y, int64_t y_row_stride, int64_t M, int64_t K, int64_t B,
+                                const void *workspace, size_t workspace_bytes, int path, int gemm_variant, int splitk, void *stream) {
+    if (const int frc = fault_status()) return frc;
+    return mul_mat_impl(type, W, w_row_bytes, nullptr, 0, Y, y_row_stride, M, K, B, (void *)workspace, workspace_bytes, path, gemm_variant, splitk,
+                        cdna4_epilogue{}, stream);
 }
 // n MUL_MATs of ONE activation row (B = 1) in ONE launch: wq / wk / wv, w_gate / w_up of a decoded token (round 6).  Matrices of one type and K; bias[i] may be null.
 // Bit-identical to n ggml_cdna4_mul_mat[_fused] calls with B = 1 (the same kernel body per matrix).  Returns -2 where the call has no grouped form (the caller issues the
 // separate calls): types outside the five headline formats, a K the one-launch decode does not take, misaligned rows.
-int ggml_cdna4_mul_mat_group(int type, int n, const void *const *W, const int64_t *w_row_bytes, const int64_t *M, float *const *Y, const float *const *bias, const float *X, int64_t K, void *stream) {
+int ggml_cdna4_mul_mat_group(int type, int n, const void *const *W, const int64_t *w_row_bytes, const int64_t *M, float *const *Y, const float *const *bias,
+                             const float *X, int64_t K, void *stream) {
     if (const int frc = fault_status()) return frc;
-    if (n < 1 || n > CDNA4_GEMV_GROUP_MAX || !W || !w_row_bytes || !M || !Y || !X) { cdna4_set_error_msg("mul_mat_group: 1 .. 4 matrices"); return -2; }
-    if (!(type == CDNA4_Q4_K || type == CDNA4_Q5_K || type == CDNA4_Q6_K || type == CDNA4_Q4_0 || type == CDNA4_Q8_0) || K <= 0 || ggml_cdna4_row_size(type, K) == 0 ||
-        !cdna4_gemv_fused_supported(type, K, 1) || ((uintptr_t)X & 15)) { cdna4_set_error_msg("mul_mat_group: no grouped form for this type / K / alignment"); return -2; }
+    const char *why = nullptr;
+    if (n < 1 || n > CDNA4_GEMV_GROUP_MAX || !W || !w_row_bytes || !M || !Y || !X) why = "mul_mat_group: 1 .. 4 matrices";
+    else if (!(type == CDNA4_Q4_K || type == CDNA4_Q5_K || type == CDNA4_Q6_K || type == CDNA4_Q4_0 || type == CDNA4_Q8_0)) why = "mul_mat_group: no grouped form for this type";
     cdna4_gemv_group g{};
     g.K = (int)K;
-    for (int i = 0; i < n; i++) {
-        if (M[i] <= 0 || M[i] > 0x7fffffff || !W[i] || !Y[i] || (((uintptr_t)W[i] | (uintptr_t)w_row_bytes[i]) & ((type == CDNA4_Q4_K || type == CDNA4_Q5_K) ? 15 : 1))) { cdna4_set_error_msg("mul_mat_group: bad or misaligned matrix"); return -2; }
-        if (use_mmq(type, M[i], K, 1) || resolve_path(type, GGML_CDNA4_PATH_AUTO, M[i], K, 1) != GGML_CDNA4_PATH_GEMV) { cdna4_set_error_msg("mul_mat_group: a matrix whose single call is not the one-launch GEMV"); return -2; }
+    for (int i = 0; i < n && !why; i++) {
+        const int w_mask = (type == CDNA4_Q4_K || type == CDNA4_Q5_K) ? 15 : 1;
+        if (M[i] <= 0 || M[i] > 0x7fffffff || !W[i] || !Y[i] || (((uintptr_t)W[i] | (uintptr_t)w_row_bytes[i]) & w_mask)) why = "mul_mat_group: bad or misaligned matrix";
+        else if (plan_mul_mat(type, W[i], w_row_bytes[i], X, K, M[i], K, 1, GGML_CDNA4_PATH_AUTO, 0, 0, nullptr).kind != MM_GEMV_1)
+            why = "mul_mat_group: a matrix whose single call is not the one-launch GEMV (K, alignment)";
         g.W[i] = (const uint8_t *)W[i]; g.w_row_bytes[i] = w_row_bytes[i]; g.Y[i] = Y[i]; g.M[i] = (int)M[i]; g.bias[i] = bias ? bias[i] : nullptr;
     }
+    if (why) { cdna4_set_error_msg(why); return -2; }
     return cdna4_launch_gemv_q_fused_grp(type, g, n, X, (hipStream_t)stream);
 }
-// the GEMV routes (B <= 8) apply the tail where the element is reduced, and so does the Q4_K GEMM (k_gemm_kq_t64, on 16-byte-aligned rows: what every
-// ggml buffer of the plug-in and every torch allocation gives); the older MFMA GEMM kernels write the product first (k_epilogue behind them)
-int ggml_cdna4_mul_mat_fused_residual_may_alias(int type, int64_t M, int64_t K, int64_t B) {
-    if (resolve_path(type, GGML_CDNA4_PATH_AUTO, M, K, B) == GGML_CDNA4_PATH_GEMV) return 1;
-    // GEMM route: yes where the kernel AUTO picks carries the tail in its store (every element is read and written by the same lane) — asked of the routing
-    // itself, for contiguous 256-byte-aligned operands (the call re-checks with the real pointers)
-    cdna4_epilogue e{}; e.act = 1;
-    return cdna4_gemm_q_fuses_tail(gemm_args_of(type, (const void *)(uintptr_t)256, (int64_t)ggml_cdna4_row_size(type, K), (const void *)(uintptr_t)256, (float *)(uintptr_t)256, M, M, K, B, 0, 0, e)) ? 1 : 0;
-}
-// the route ggml_cdna4_mul_mat(path = AUTO) takes for a contiguous, 256-byte-aligned call of this shape on the current device — host logic only, no launch, no scratch:
-//   1 one launch (activation quantizer inside the GEMV)     2 quantize + GEMV (columns staged in LDS)     3 quantize + int8 matrix-core kernel
-//   10 quantize + k_gemm_kq_t64     11 ONE launch: the quantizer inside k_gemm_kq_t64 (resident grids on an owned device)     12 + k_gemm_r8     13 + a 128 x 128-tile kernel     14 + an older per-lane-load GEMM;   + 100: behind an exact re-encoding of the weights
-static int route_of(int type, const void *W, int64_t w_row_bytes, int64_t M, int64_t K, int64_t B);
-int ggml_cdna4_mul_mat_route(int type, int64_t M, int64_t K, int64_t B) {
-    return route_of(type, (const void *)(uintptr_t)256, (int64_t)ggml_cdna4_row_size(type, K), M, K, B);
-}
-// the same for a concrete weight matrix: sees its alignment, its row stride and a RESIDENT image registered for it (Q4_0 with an image: 10 / 12 instead of 13)
+// the integer-dot kernels apply the tail where the element is reduced, and so do k_gemm_kq_t64 / k_gemm_r8 and the 128 x 128-tile kernels outside their
+// atomic-sum split; the older MFMA GEMM kernels write the product first (k_epilogue behind them).  The call re-checks with the real pointers.
+int ggml_cdna4_mul_mat_fused_residual_may_alias(int type, int64_t M, int64_t K, int64_t B) { return plan_query(type, M, K, B).tail_in_store ? 1 : 0; }
+// the route of the AUTO call on the current device, host logic only (the numbers: include/ggml_cdna4.h; 11 = ONE launch, the quantizer inside k_gemm_kq_t64)
+int ggml_cdna4_mul_mat_route(int type, int64_t M, int64_t K, int64_t B) { return plan_query(type, M, K, B).route_id; }
+// the same for a concrete weight matrix: what the call on THIS matrix launches, given its alignment, row stride and resident image
 int ggml_cdna4_mul_mat_route_of(int type, const void *W, int64_t w_row_bytes, int64_t M, int64_t K, int64_t B) {
     if (!W || w_row_bytes < (int64_t)ggml_cdna4_row_size(type, K)) return 0;
-    return route_of(type, W, w_row_bytes, M, K, B);
+    return plan_query(type, W, w_row_bytes, M, K, B).route_id;
 }
-static int route_of(int type, const void *W, int64_t w_row_bytes, int64_t M, int64_t K, int64_t B) {
-    if (!is_q(type) || M <= 0 || B <= 0 || K <= 0 || ggml_cdna4_row_size(type, K) == 0) return 0;
-    if (cdna4_convert_weights_kmul(type) == 1) {
-        const int tgt = cdna4_convert_weights_target(type);
-        if (tgt >= 0 && tgt != type && B >= 9 && use_mmq(tgt, M, K, B)) return 103;
-    }
-    if (use_mmq(type, M, K, B)) return 3;
-    const int path = resolve_path(type, GGML_CDNA4_PATH_AUTO, M, K, B);
-    if (path == GGML_CDNA4_PATH_GEMV) {
-        const int64_t nbt = B <= 1 ? 1 : (B <= 2 ? 2 : (B <= 4 ? 4 : 8));
-        return (cdna4_gemv_fused_supported(type, K, B) && (B == 1 || nbt * K <= 32768)) ? 1 : 2;
-    }
-    cdna4_gemm_args ra = gemm_args_of(type, W, w_row_bytes, (const void *)(uintptr_t)256, (float *)(uintptr_t)256, M, M, K, B, 0, 0, cdna4_epilogue{});
-    ra.xf = (const float *)(uintptr_t)256; ra.xf_row_elems = K;       // (the call hands its fp32 rows over: the one-launch step is a candidate)
-    return cdna4_gemm_q_route(ra);
-}
-// the checks ggml_cdna4_mul_mat_fused and its pre-quantized twin share: 0, or the error status
-static int fused_tail_ok(int type, const void *W, int64_t w_row_bytes, float *Y, int64_t y_row_stride, int64_t M, int64_t K, int64_t B, int act,
-                         const float *residual, int64_t residual_row_stride, const void *workspace) {
+// the checks ggml_cdna4_mul_mat_fused and its pre-quantized twin (X == nullptr) share: 0, or the error status
+static int fused_tail_ok(int type, const void *W, int64_t w_row_bytes, const float *X, int64_t x_row_stride, float *Y, int64_t y_row_stride,
+                         int64_t M, int64_t K, int64_t B, int act, const float *residual, int64_t residual_row_stride, const void *workspace) {
     if (act != 0 && act != 1) return cdna4_set_error_msg("mul_mat_fused: act is 0 (none) or 1 (GELU)");
     if (residual && M > 0 && B > 0) {
         const char *r0 = (const char *)residual, *r1 = (const char *)(residual + (B - 1) * residual_row_stride + M);
         const char *y0 = (const char *)Y, *y1 = (const char *)(Y + (B - 1) * y_row_stride + M);
         const bool overlap = r0 < y1 && y0 < r1, exact = residual == Y && residual_row_stride == y_row_stride;
-        bool ok = exact && ggml_cdna4_mul_mat_fused_residual_may_alias(type, M, K, B);
-        if (ok && resolve_path(type, GGML_CDNA4_PATH_AUTO, M, K, B) == GGML_CDNA4_PATH_GEMM)     // the query cannot see the pointers: the fused GEMM needs aligned rows
-            ok = cdna4_gemm_q_fuses_tail(gemm_args_of(type, W, w_row_bytes, workspace, Y, y_row_stride, M, K, B, 0, 0, cdna4_epilogue{}));
-        if (overlap && !ok)
-            return cdna4_set_error_msg("mul_mat_fused: residual overlaps Y (only an exact alias is allowed, and only where ggml_cdna4_mul_mat_fused_residual_may_alias says so)");
+        // an exact alias needs the tail in the store: by the shape (what the query told the caller) and with these pointers (aligned rows)
+        if (overlap && !(exact && plan_query(type, M, K, B).tail_in_store &&
+                         plan_mul_mat(type, W, w_row_bytes, X, x_row_stride, M, K, B, GGML_CDNA4_PATH_AUTO, 0, 0, workspace).tail_in_store))
+            return cdna4_set_error_msg("mul_mat_fused: residual overlaps Y (only an exact alias is allowed, and only where "
+                                       "ggml_cdna4_mul_mat_fused_residual_may_alias says so)");
     }
     return 0;
 }
@@ -469,7 +471,7 @@ int ggml_cdna4_mul_mat_fused(int type, const void *W, int64_t w_row_bytes, const
                              int64_t M, int64_t K, int64_t B, const float *bias, int act, const float *residual, int64_t residual_row_stride,
                              void *workspace, size_t workspace_bytes, void *stream) {
     if (const int frc = fault_status()) return frc;
-    if (const int rc = fused_tail_ok(type, W, w_row_bytes, Y, y_row_stride, M, K, B, act, residual, residual_row_stride, workspace)) return rc;
+    if (const int rc = fused_tail_ok(type, W, w_row_bytes, X, x_row_stride, Y, y_row_stride, M, K, B, act, residual, residual_row_stride, workspace)) return rc;
     cdna4_epilogue e{}; e.bias = bias; e.resid = residual; e.resid_row_stride = residual_row_stride; e.act = act;
     return mul_mat_impl(type, W, w_row_bytes, X, x_row_stride, Y, y_row_stride, M, K, B, workspace, workspace_bytes, GGML_CDNA4_PATH_AUTO, 0, 0, e, stream);
 }
@@ -478,23 +480,10 @@ int ggml_cdna4_mul_mat_fused(int type, const void *W, int64_t w_row_bytes, const
 // the activations have not changed since the previous call on this workspace asks for the key of the image each call leaves there; equal non-zero keys (and equal X, row
 // stride, K, B) mean the second call can be ggml_cdna4_mul_mat_prepared[_fused] with path AUTO — the same kernels on the same image, bit-identical, one launch fewer.
 //   0: the call leaves no reusable image (one-launch decode / few-row forms quantize inside the kernel; re-encoded formats on the int8 matrix cores use their target's image)
-uint32_t ggml_cdna4_act_image_key(int type, int64_t M, int64_t K, int64_t B) {
-    if (!is_q(type) || M <= 0 || B <= 0 || K <= 0 || ggml_cdna4_row_size(type, K) == 0) return 0;
-    if (cdna4_convert_weights_kmul(type) == 1) {
-        const int tgt = cdna4_convert_weights_target(type);
-        if (tgt >= 0 && tgt != type && B >= 9 && use_mmq(tgt, M, K, B)) return 0;
-    }
-    const bool mmq = use_mmq(type, M, K, B);
-    const int path = resolve_path(type, GGML_CDNA4_PATH_AUTO, M, K, B);
-    if (path != GGML_CDNA4_PATH_GEMM && !mmq) return 0;                 // (the GEMV forms below the matrix-core kernels: one launch, or their own staged variant)
-    return 1u | (is_kq(type) ? 2u : 0u) | (cdna4_is_q81(type) ? 4u : 0u) | (cdna4_convert_weights_kmul(type) == 2 ? 8u : 0u) | (path == GGML_CDNA4_PATH_GEMM ? 16u : 0u);
-}
-// the key of the call on a CONCRETE weight matrix: a few-row call (int8 class) on rows that are not 16-byte aligned does not take the int8 matrix-core kernel — it may
-// quantize inside a one-launch GEMV and leave the workspace untouched (mul_mat_impl) — so such a call names no image
+uint32_t ggml_cdna4_act_image_key(int type, int64_t M, int64_t K, int64_t B) { return plan_query(type, M, K, B).image_key; }
+// the key of the call on a CONCRETE weight matrix: rows the int8 matrix-core kernel cannot read take a GEMV form, which names no image
 uint32_t ggml_cdna4_act_image_key_of(int type, const void *W, int64_t w_row_bytes, int64_t M, int64_t K, int64_t B) {
-    const uint32_t key = ggml_cdna4_act_image_key(type, M, K, B);
-    if (key && !(key & 16u) && (((uintptr_t)W | (uintptr_t)w_row_bytes) & (type == CDNA4_Q6_K ? 1 : 15))) return 0;
-    return key;
+    return plan_query(type, W, w_row_bytes, M, K, B).image_key;
 }
 // NORM / RMS_NORM [* gain] [+ shift] that ALSO leaves, in `workspace`, the activation image a following ggml_cdna4_mul_mat(type, .., X = dst, K = dst->ne[0], B = its rows)
 // would build — for the calls whose ggml_cdna4_act_image_key is the K-quants' fp16 GEMM image (19): the MUL_MATs of dst then run ggml_cdna4_mul_mat_prepared[_fused] and
@@ -528,24 +517,25 @@ int ggml_cdna4_mul_mat_prepared_fused(int type, const void *W, int64_t w_row_byt
                                       const float *bias, int act, const float *residual, int64_t residual_row_stride,
                                       const void *workspace, size_t workspace_bytes, void *stream) {
     if (const int frc = fault_status()) return frc;
-    if (const int rc = fused_tail_ok(type, W, w_row_bytes, Y, y_row_stride, M, K, B, act, residual, residual_row_stride, workspace)) return rc;
-    if (!ggml_cdna4_act_image_key(type, M, K, B)) return cdna4_set_error_msg("mul_mat_prepared_fused: a call of this shape has no prepared form (ggml_cdna4_act_image_key == 0)");
+    if (const int rc = fused_tail_ok(type, W, w_row_bytes, nullptr, 0, Y, y_row_stride, M, K, B, act, residual, residual_row_stride, workspace)) return rc;
+    if (!plan_query(type, M, K, B).image_key) return cdna4_set_error_msg("mul_mat_prepared_fused: a call of this shape has no prepared form (ggml_cdna4_act_image_key == 0)");
     cdna4_epilogue e{}; e.bias = bias; e.resid = residual; e.resid_row_stride = residual_row_stride; e.act = act;
-    bool tail_done = false;
-    const int rc = mul_mat_prepared_impl(type, W, w_row_bytes, Y, y_row_stride, M, K, B, workspace, workspace_bytes, GGML_CDNA4_PATH_AUTO, 0, 0, e, &tail_done, stream);
-    if (rc || tail_done) return rc;
-    return cdna4_launch_epilogue(Y, y_row_stride, M, B, e, (hipStream_t)stream);
+    return mul_mat_impl(type, W, w_row_bytes, nullptr, 0, Y, y_row_stride, M, K, B, (void *)workspace, workspace_bytes, GGML_CDNA4_PATH_AUTO, 0, 0, e, stream);
 }
 
+// the resident Q4_0R image of a Q4_0 expert stack (ggml's 3-D expert tensor: the experts' rows back to back; found by the stack's pointer, like ggml_cdna4_mul_mat finds a
+// matrix's), or nullptr: with it the stack runs on Q4_K's grouped kernels (row stride (K / 256) * 144)
+static const uint8_t *moe_q4_0r_image(int type, const void *as, int64_t w_row_bytes, int64_t w_expert_bytes, int64_t M, int64_t K, int64_t n_expert) {
+    if (type != CDNA4_Q4_0 || K % 256 || w_expert_bytes != M * w_row_bytes) return nullptr;
+    const uint8_t *img = cdna4_resident_lookup(CDNA4_Q4_0, as, w_row_bytes, M * n_expert, K);
+    return img && !((uintptr_t)img & 15) ? img : nullptr;
+}
 // the work-queue form's choice for a call (shared by the call, its `prepared` twin and the key): Q4_K experts, or Q4_0 experts whose stack has a resident Q4_0R image
 struct moe_sk_pick { int type = -1; const uint8_t *W = nullptr; int64_t row = 0, exp = 0; };
 static moe_sk_pick moe_sk_pick_of(int type, const void *as, int64_t w_row_bytes, int64_t w_expert_bytes, int64_t M, int64_t K, int64_t n_expert, int64_t n_used, int64_t n_b, int64_t n_tok) {
     moe_sk_pick r; r.W = (const uint8_t *)as; r.row = w_row_bytes; r.exp = w_expert_bytes;
     if (type == CDNA4_Q4_K && !(((uintptr_t)as | (uintptr_t)w_row_bytes | (uintptr_t)w_expert_bytes) & 15)) r.type = CDNA4_Q4_K;
-    else if (type == CDNA4_Q4_0 && K % 256 == 0 && w_expert_bytes == M * w_row_bytes) {
-        const uint8_t *img = cdna4_resident_lookup(CDNA4_Q4_0, as, w_row_bytes, M * n_expert, K);
-        if (img && !((uintptr_t)img & 15)) { r.type = CDNA4_Q4_0R; r.W = img; r.row = (K / 256) * 144; r.exp = M * r.row; }
-    }
+    else if (const uint8_t *img = moe_q4_0r_image(type, as, w_row_bytes, w_expert_bytes, M, K, n_expert)) { r.type = CDNA4_Q4_0R; r.W = img; r.row = (K / 256) * 144; r.exp = M * r.row; }
     // (CDNA4_MMQ_IDS=2 — a coverage / measurement knob — asks for the int8 matrix-core kernels where there are few rows per expert)
     static const bool mmq_ids_forced = getenv("CDNA4_MMQ_IDS") && atoi(getenv("CDNA4_MMQ_IDS")) == 2;
     if (mmq_ids_forced && n_tok * n_used <= 32 * n_expert) r.type = -1;
@@ -601,36 +591,29 @@ static int mul_mat_id_impl(bool front_in_place, int type, const void *as, int64_
     // prefill-sized mixture-of-experts batches: group the (token, slot) rows by expert on the device and run ONE MFMA GEMM launch over
     // the (expert, activation tile) table — every expert's weights are read once per m-tile instead of once per column
     // (ggml_compute_forward_mul_mat_id groups the same way on the host: ggml-cpu.c:7648-7781)
-    if (front_in_place && !moe_grouped_call(type, as, w_row_bytes, w_expert_bytes, b, b_row_stride, K, n_expert, n_used, n_tok, workspace)) { cdna4_set_error_msg("mul_mat_id_prepared: misaligned operands"); return -2; }
-    if (moe_grouped_call(type, as, w_row_bytes, w_expert_bytes, b, b_row_stride, K, n_expert, n_used, n_tok, workspace)) {
-        // Q4_K experts, and Q4_0 experts whose stack has a RESIDENT Q4_0R image (ggml's 3-D expert tensor, rows back to back; found by the stack's pointer): the stream-k form —
-        // TWO launches (planner + token-order quantizer; one persistent grouped GEMM that gathers its rows), round 6
-        {
-            const moe_sk_pick pk = moe_sk_pick_of(type, as, w_row_bytes, w_expert_bytes, M, K, n_expert, n_used, n_b, n_tok);
-            const int sk_type = pk.type; const uint8_t *skW = pk.W; const int64_t sk_row = pk.row, sk_exp = pk.exp;
-            if (sk_type >= 0) {
-                const moe_sk_view sv = moe_sk_carve(K, n_expert, n_used, n_b, n_tok, workspace);
-                if (workspace_bytes >= sv.total) {
-                    // cost of one (tile, m-tile, superblock) unit by the tile's fragments in use (1 .. 4), relative.  FLAT, by measurement: the k loop is bound by its unpack /
-                    // issue work, which does not depend on the fragments — a tile with one fragment in use takes 1.78-1.91 us per superblock, a full one 1.86-1.92
-                    // (profiles/r06/moe_sk_trace_*.txt), with or without the activation DMA of the empty fragments; weights that call light tiles cheaper lost: 8 x 2 x 512 x 4096^2,
-                    // us per call, one box: 10,10,10,10 72.2 | 8,9,10,10 79.8 | 7,8,9,10 85.0 | 6,8,9,10 90.7 | 5,7,9,10 98.1 | 4,6,8,10 107.6 (CDNA4_SK_CW=a,b,c,d: measurement knob)
-                    struct sk_costs { int c[4]; sk_costs() : c{10, 10, 10, 10} { int t4[4]; const char *ev = getenv("CDNA4_SK_CW");
-                        if (ev && sscanf(ev, "%d,%d,%d,%d", &t4[0], &t4[1], &t4[2], &t4[3]) == 4 && t4[0] > 0 && t4[1] > 0 && t4[2] > 0 && t4[3] > 0 && t4[3] < 256) for (int i = 0; i < 4; i++) c[i] = t4[i]; } };
-                    static const sk_costs costs;
-                    const int *cw = costs.c;
-                    const int G = cdna4_gemm_sk_spans();
-                    const int64_t upt = ((M + 127) / 128) * (K / 256);
-                    // (prepared: the front of an earlier call with the same b, ids and shape is in place)
-                    int rc = front_in_place ? 0 : cdna4_launch_moe_sk_front(ids, ids_tok_stride, (int)n_tok, (int)n_used, (int)n_b, (int)n_expert, (int)sv.ntile_cap, (int)upt, G, cw, sv.tile_rec, sv.wg_begin,
-                                                                            b, b_row_stride, K, sk_type == CDNA4_Q4_K, sv.xh, (hipStream_t)stream);
-                    if (rc) return rc;
-                    cdna4_gemm_args a{};
-                    a.type = sk_type; a.W = skW; a.w_row_bytes = sk_row; a.xh = sv.xh; a.xh_row_elems = K;
-                    a.Y = dst; a.y_row_elems = dst_row_stride; a.M = (int)M; a.K = (int)K; a.B = (int)sv.n_rows;
-                    return cdna4_launch_gemm_sk(a, sv.tile_rec, sv.wg_begin, G, sk_exp, (hipStream_t)stream);
-                }
-            }
+    const bool grouped = moe_grouped_call(type, as, w_row_bytes, w_expert_bytes, b, b_row_stride, K, n_expert, n_used, n_tok, workspace);
+    if (front_in_place && !grouped) { cdna4_set_error_msg("mul_mat_id_prepared: misaligned operands"); return -2; }
+    if (grouped) {
+        // Q4_K experts, and Q4_0 experts whose stack has a RESIDENT Q4_0R image: the stream-k form — TWO launches (planner + token-order quantizer; one persistent grouped
+        // GEMM that gathers its rows), round 6
+        const moe_sk_pick pk = moe_sk_pick_of(type, as, w_row_bytes, w_expert_bytes, M, K, n_expert, n_used, n_b, n_tok);
+        const moe_sk_view sv = moe_sk_carve(K, n_expert, n_used, n_b, n_tok, workspace);
+        if (pk.type >= 0 && workspace_bytes >= sv.total) {
+            // cost of one (tile, m-tile, superblock) unit by the tile's fragments in use (1 .. 4), relative.  FLAT, by measurement: the k loop is bound by its unpack /
+            // issue work, which does not depend on the fragments — a tile with one fragment in use takes 1.78-1.91 us per superblock, a full one 1.86-1.92
+            // (profiles/r06/moe_sk_trace_*.txt), with or without the activation DMA of the empty fragments; weights that call light tiles cheaper lost: 8 x 2 x 512 x 4096^2,
+            // us per call, one box: 10,10,10,10 72.2 | 8,9,10,10 79.8 | 7,8,9,10 85.0 | 6,8,9,10 90.7 | 5,7,9,10 98.1 | 4,6,8,10 107.6 (CDNA4_SK_CW=a,b,c,d: measurement knob)
+            struct sk_costs { int c[4]; sk_costs() : c{10, 10, 10, 10} { int t4[4]; const char *ev = getenv("CDNA4_SK_CW");
+                if (ev && sscanf(ev, "%d,%d,%d,%d", &t4[0], &t4[1], &t4[2], &t4[3]) == 4 && t4[0] > 0 && t4[1] > 0 && t4[2] > 0 && t4[3] > 0 && t4[3] < 256) for (int i = 0; i < 4; i++) c[i] = t4[i]; } };
+            static const sk_costs costs;
+            const int G = cdna4_gemm_sk_spans();
+            const int64_t upt = ((M + 127) / 128) * (K / 256);
+            // (prepared: the front of an earlier call with the same b, ids and shape is in place)
+            const int rc = front_in_place ? 0 : cdna4_launch_moe_sk_front(ids, ids_tok_stride, (int)n_tok, (int)n_used, (int)n_b, (int)n_expert, (int)sv.ntile_cap, (int)upt, G, costs.c,
+                                                                          sv.tile_rec, sv.wg_begin, b, b_row_stride, K, pk.type == CDNA4_Q4_K, sv.xh, (hipStream_t)stream);
+            if (rc) return rc;
+            const cdna4_gemm_args a = gemm_args_of(pk.type, pk.W, pk.row, sv.xh, dst, dst_row_stride, M, K, sv.n_rows, 0, 0, cdna4_epilogue{});
+            return cdna4_launch_gemm_sk(a, sv.tile_rec, sv.wg_begin, G, pk.exp, (hipStream_t)stream);
         }
         if (front_in_place) { cdna4_set_error_msg("mul_mat_id_prepared: this call does not take the work-queue form"); return -2; }
         const moe_view mv = moe_carve(K, n_expert, n_used, n_tok, workspace);
@@ -647,53 +630,45 @@ static int mul_mat_id_impl(bool front_in_place, int type, const void *as, int64_
             static const bool all_mmq_ids = getenv("CDNA4_MMQ_IDS") && atoi(getenv("CDNA4_MMQ_IDS")) == 2;
             if (!no_mmq_ids && (type != CDNA4_Q4_K || all_mmq_ids) && n_tok * n_used <= 32 * n_expert && cdna4_mmq_ids_supported(type, K) &&
                 !(((uintptr_t)as | (uintptr_t)w_row_bytes | (uintptr_t)w_expert_bytes) & (type == CDNA4_Q6_K ? 1 : 15))) {
-                int8_t *iq = (int8_t *)mv.xh;
-                float *id_ = (float *)((uint8_t *)mv.xh + align256((size_t)mv.img_rows * K));
-                int16_t *ibs = (int16_t *)((uint8_t *)id_ + align256((size_t)mv.img_rows * (K / 32) * 4));
-                rc = is_kq(type) ? cdna4_launch_quantize_q8_K_gather_i8(b, b_row_stride, K, mv.img_rows, mv.img_src, iq, id_, ibs, (hipStream_t)stream)
-                                 : cdna4_launch_quantize_q8_0_gather_i8(b, b_row_stride, K, mv.img_rows, mv.img_src, iq, id_, (hipStream_t)stream);
+                ws_view iv{};                                                // the int8 image: [qs][d][bsums (K-quants)]
+                iv.qs = (int8_t *)mv.xh;
+                iv.d = (float *)((uint8_t *)mv.xh + align256((size_t)mv.img_rows * K));
+                int16_t *ibs = (int16_t *)((uint8_t *)iv.d + align256((size_t)mv.img_rows * (K / 32) * 4));
+                rc = is_kq(type) ? cdna4_launch_quantize_q8_K_gather_i8(b, b_row_stride, K, mv.img_rows, mv.img_src, iv.qs, iv.d, ibs, (hipStream_t)stream)
+                                 : cdna4_launch_quantize_q8_0_gather_i8(b, b_row_stride, K, mv.img_rows, mv.img_src, iv.qs, iv.d, (hipStream_t)stream);
                 if (rc) return rc;
-                cdna4_gemv_args g{};
-                g.type = type; g.W = (const uint8_t *)as; g.w_row_bytes = w_row_bytes; g.qs = iq; g.d = id_; g.bsums = is_kq(type) ? ibs : nullptr;
-                g.Y = dst; g.y_col_stride = dst_row_stride; g.M = (int)M; g.K = (int)K; g.ncol = (int)mv.img_rows;
+                iv.bsums = is_kq(type) ? ibs : nullptr;
+                const cdna4_gemv_args g = gemv_args_of(type, as, w_row_bytes, iv, dst, dst_row_stride, M, K, mv.img_rows, cdna4_epilogue{});
                 return cdna4_launch_mmq_ids(g, mv.tile_expert, mv.img_dst, w_expert_bytes, (hipStream_t)stream);
             }
             rc = is_kq(type) ? cdna4_launch_quantize_q8_K_gather(b, b_row_stride, K, mv.img_rows, mv.img_src, mv.xh, (hipStream_t)stream)
                              : cdna4_launch_quantize_q8_0_gather(b, b_row_stride, K, mv.img_rows, mv.img_src, mv.xh, (hipStream_t)stream);
             if (rc) return rc;
-            cdna4_gemm_args a{};
-            a.type = type; a.W = (const uint8_t *)as; a.w_row_bytes = w_row_bytes; a.xh = mv.xh; a.xh_row_elems = K;
-            a.Y = dst; a.y_row_elems = dst_row_stride; a.M = (int)M; a.K = (int)K; a.B = (int)mv.img_rows;
-            // Q4_0 experts with a RESIDENT Q4_0R image of the whole stack (the experts' rows back to back: ggml's 3-D expert tensor): Q4_K's grouped kernel instead of the
-            // per-lane-load one (round 5; the image is found by the stack's pointer, like ggml_cdna4_mul_mat finds a matrix's)
-            if (type == CDNA4_Q4_0 && K % 256 == 0 && w_expert_bytes == M * w_row_bytes) {
-                const uint8_t *img = cdna4_resident_lookup(CDNA4_Q4_0, as, w_row_bytes, M * n_expert, K);
-                if (img && !((uintptr_t)img & 15)) {
-                    a.type = CDNA4_Q4_0R; a.W = img; a.w_row_bytes = (K / 256) * 144;
-                    return cdna4_launch_gemm_t64_ids(a, mv.tile_expert, mv.img_dst, M * a.w_row_bytes, (hipStream_t)stream);
-                }
+            cdna4_gemm_args a = gemm_args_of(type, as, w_row_bytes, mv.xh, dst, dst_row_stride, M, K, mv.img_rows, 0, 0, cdna4_epilogue{});
+            // Q4_0 experts with a RESIDENT Q4_0R image of the whole stack: Q4_K's grouped kernel instead of the per-lane-load one (round 5)
+            if (const uint8_t *img = moe_q4_0r_image(type, as, w_row_bytes, w_expert_bytes, M, K, n_expert)) {
+                a.type = CDNA4_Q4_0R; a.W = img; a.w_row_bytes = (K / 256) * 144;
+                return cdna4_launch_gemm_t64_ids(a, mv.tile_expert, mv.img_dst, M * a.w_row_bytes, (hipStream_t)stream);
             }
             return cdna4_launch_gemm_ids(a, mv.tile_expert, mv.img_dst, w_expert_bytes, (hipStream_t)stream);   // Q4_K: k_gemm_kq_t64<.., IDS>; Q5_K / Q6_K / Q4_0 / Q8_0: k_gemm_q<.., IDS>
         }
     }
+    // the MUL_MAT_ID columns of a GEMV launch: column c = (token, slot)
+    const auto gemv_ids = [&](cdna4_gemv_args g) {
+        g.ids = ids; g.ids_tok_stride = ids_tok_stride; g.w_expert_bytes = w_expert_bytes; g.n_used = (int)n_used; g.n_b = (int)n_b; g.n_expert = (int)n_expert;
+        return g;
+    };
     if (n_tok == 1 && n_used <= 65535 && cdna4_gemv_fused_supported(type, K, 1) && !(((uintptr_t)b | (uintptr_t)(b_row_stride * 4)) & 15)) {
         // single-token decode of a mixture-of-experts layer: one launch, the activation quantizer runs inside the GEMV
-        cdna4_gemv_args g{};
-        g.type = type; g.W = (const uint8_t *)as; g.w_row_bytes = w_row_bytes; g.Y = dst; g.y_col_stride = dst_row_stride;
-        g.M = (int)M; g.K = (int)K; g.ncol = (int)n_used;
-        g.ids = ids; g.ids_tok_stride = ids_tok_stride; g.w_expert_bytes = w_expert_bytes; g.n_used = (int)n_used; g.n_b = (int)n_b; g.n_expert = (int)n_expert;
+        const cdna4_gemv_args g = gemv_ids(gemv_args_of(type, as, w_row_bytes, ws_view{}, dst, dst_row_stride, M, K, n_used, cdna4_epilogue{}));
         return cdna4_launch_gemv_q_fused_ids(g, b, b_row_stride, (hipStream_t)stream);
     }
     if (!workspace || ((uintptr_t)workspace & 255)) return cdna4_set_error_msg("mul_mat_id: workspace must be 256-byte aligned");
     const ws_view v = carve(type, K, nact, workspace);
     if (workspace_bytes < v.total) return cdna4_set_error_msg("mul_mat_id: workspace too small");
-    int rc = ggml_cdna4_prepare_act(type, b, b_row_stride, K, nact, workspace, workspace_bytes, GGML_CDNA4_PATH_GEMV, stream);
+    const int rc = ggml_cdna4_prepare_act(type, b, b_row_stride, K, nact, workspace, workspace_bytes, GGML_CDNA4_PATH_GEMV, stream);
     if (rc) return rc;
-    cdna4_gemv_args g{};
-    g.type = type; g.W = (const uint8_t *)as; g.w_row_bytes = w_row_bytes; g.qs = v.qs; g.d = v.d; g.bsums = v.bsums;
-    g.Y = dst; g.y_col_stride = dst_row_stride; g.M = (int)M; g.K = (int)K; g.ncol = (int)(n_tok * n_used);
-    g.ids = ids; g.ids_tok_stride = ids_tok_stride; g.w_expert_bytes = w_expert_bytes; g.n_used = (int)n_used; g.n_b = (int)n_b; g.n_expert = (int)n_expert;
-    return cdna4_launch_gemv_q(g, (hipStream_t)stream);
+    return cdna4_launch_gemv_q(gemv_ids(gemv_args_of(type, as, w_row_bytes, v, dst, dst_row_stride, M, K, n_tok * n_used, cdna4_epilogue{})), (hipStream_t)stream);
 }
 
 }  // extern "C"

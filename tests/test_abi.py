@@ -158,6 +158,58 @@ print(json.dumps({"kq_gemm": [f(12, 4096, 4096, 512), f(12, 1024, 4096, 512), f(
     assert got["of"] == [3, 0, 0, 19, 3, 0]
 
 
+def test_route_key_and_tail_queries_read_one_plan(built):
+    """capi.hip: ggml_cdna4_mul_mat_route[_of], ggml_cdna4_act_image_key[_of] and ggml_cdna4_mul_mat_fused_residual_may_alias are field reads of ONE routing plan
+    (plan_mul_mat), the plan the call itself launches from — so they cannot disagree.  Over 12 formats x 7 M x 9 K x 18 B, in the default and the owned mode, host logic only:
+      (a) route == 0 (not a supported call) => key == 0
+      (b) for a supported call: key == 0 <=> route % 100 in {1, 2} (the GEMV forms) or route == 103 (re-encoded onto the int8 matrix cores: the target's image)
+      (c) route == 3 <=> key != 0 without the GEMM bit (16): the int8 image          (d) route % 100 >= 10 <=> key has the GEMM bit
+      (e) route % 100 < 10 => the tail rides in the store (may_alias == 1)
+      (f) on aligned rows the query of a concrete matrix answers what the shape-only query answers
+      (g) for EVERY alignment of the weights: route_of == 3 => key_of names the int8 image (bit 0 set, GEMM bit clear) — route_of used to answer 3 for rows the int8
+          matrix-core kernel cannot read, where the call takes a GEMV form and key_of said 0"""
+    import subprocess, sys, json
+    code = r"""
+import ctypes as C, itertools, json, sys
+L = C.CDLL(sys.argv[1])
+i64 = C.c_int64
+def fn(name, res, args):
+    f = getattr(L, name); f.restype = res; f.argtypes = args; return f
+route = fn("ggml_cdna4_mul_mat_route", C.c_int, [C.c_int, i64, i64, i64])
+route_of = fn("ggml_cdna4_mul_mat_route_of", C.c_int, [C.c_int, C.c_void_p, i64, i64, i64, i64])
+key = fn("ggml_cdna4_act_image_key", C.c_uint32, [C.c_int, i64, i64, i64])
+key_of = fn("ggml_cdna4_act_image_key_of", C.c_uint32, [C.c_int, C.c_void_p, i64, i64, i64, i64])
+alias = fn("ggml_cdna4_mul_mat_fused_residual_may_alias", C.c_int, [C.c_int, i64, i64, i64])
+rowsz = fn("ggml_cdna4_row_size", C.c_size_t, [C.c_int, i64])
+bad = {p: [] for p in "abcdefg"}
+n = routes3 = 0
+for t, m, k, b in itertools.product((12, 13, 14, 2, 8, 6, 10, 11, 3, 7, 20, 23), (32, 256, 768, 1024, 4096, 14336, 32768), (256, 768, 1024, 4032, 4096, 4160, 8192, 11008, 14336),
+                                    (1, 2, 3, 4, 5, 8, 9, 16, 32, 33, 48, 49, 64, 65, 96, 128, 512, 2048)):
+    r, ky, al, rb = route(t, m, k, b), key(t, m, k, b), alias(t, m, k, b), rowsz(t, k)
+    n += 1
+    if r == 0 and ky != 0: bad["a"].append((t, m, k, b, r, ky))
+    if r != 0 and ((r % 100 in (1, 2) or r == 103) != (ky == 0)): bad["b"].append((t, m, k, b, r, ky))
+    if (r == 3) != (ky != 0 and not ky & 16): bad["c"].append((t, m, k, b, r, ky))
+    if (r % 100 >= 10) != bool(ky & 16): bad["d"].append((t, m, k, b, r, ky))
+    if r % 100 < 10 and al != 1: bad["e"].append((t, m, k, b, r, al))
+    if rb == 0: continue
+    for w, extra in ((256, 0), (258, 0), (256, 2), (257, 0)):
+        ro, ko = route_of(t, w, rb + extra, m, k, b), key_of(t, w, rb + extra, m, k, b)
+        if (w, extra) == (256, 0) and (ro, ko) != (r, ky): bad["f"].append((t, m, k, b, r, ky, ro, ko))
+        if ro == 3 and not (ko & 1 and not ko & 16): bad["g"].append((t, m, k, b, w, extra, ro, ko))
+        routes3 += ro == 3
+print(json.dumps({"n": n, "routes3": routes3, "bad": {p: [len(v), v[:3]] for p, v in bad.items()}}))
+"""
+    for env in ({}, {"GGML_CDNA4_OWNED_DEVICE": "1"}):
+        r = subprocess.run([sys.executable, "-c", code, os.path.join(ROOT, "ggml_amd", "lib", "libcdna4_kernels.so")], capture_output=True, text=True, timeout=120,
+                           env=dict({k: v for k, v in os.environ.items() if k not in ("GGML_CDNA4_OWNED_DEVICE", "GGML_CDNA4_SHARED_DEVICE")}, CDNA4_ASSUME_CUS="256", HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1", **env))
+        assert r.returncode == 0, r.stderr[-800:]
+        got = json.loads(r.stdout.strip().splitlines()[-1])
+        assert got["n"] == 12 * 7 * 9 * 18 and got["routes3"] > 1000, got       # (the sweep ran, and the int8 matrix-core class is in it)
+        for p, (count, first) in got["bad"].items():
+            assert count == 0, (env, p, count, first)
+
+
 def test_no_cpu_fallback(built):
     """without a GPU the product must raise, not compute on the host"""
     import torch
