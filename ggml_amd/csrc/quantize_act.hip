@@ -289,7 +289,8 @@ __device__ void moe_sk_plan(const moe_sk_args &a) {
     constexpr int trs = 7, TR = 1 << trs, REC = CDNA4_SK_REC;           // rows per tile; int32 per tile record
     __shared__ int cnt[1024], tpre[1025], cpre[CDNA4_SK_MAX_TILES + 1], tmp[NW];
     __shared__ uint8_t trows[CDNA4_SK_MAX_TILES + 1];                   // rows of tile t, minus one
-    __shared__ uint16_t wtab[WTAB];                                     // the stable ranking: [chunk of the round][expert]
+    __shared__ uint16_t wtab[WTAB];                                     // the stable ranking: [chunk of the round][expert], rows of the expert in the round's earlier chunks (< CMAX * 64)
+    __shared__ uint16_t rtot[1024];                                     // several rounds: the round's rows per expert
     __shared__ int16_t ekey[CMAX * 64]; __shared__ uint8_t erank[CMAX * 64]; __shared__ int esrc[CMAX * 64];      // per pair of the round: expert (-1: none), rank inside its chunk, activation row
     int *const pos = cnt;                                               // (the counts are dead once the tiles' rows are known: the same words count the rows placed so far)
     const int tid = threadIdx.x, wv = tid >> 6, ln = tid & 63, n_pairs = a.n_tok * a.n_used, ne = a.n_expert;
@@ -297,13 +298,14 @@ __device__ void moe_sk_plan(const moe_sk_args &a) {
     // that which tile a row lands in (and with it where its K range is cut and summed) is a function of the ids alone: the launch is bit-reproducible.  Pairs are ranked in
     // CHUNKS of 64 (one wave each), a ROUND = CH chunks (CH * ne <= WTAB entries of the table, at most CMAX), chunk c of a round by wave c % NW: inside a chunk the rank among
     // equal keys by ballots over the distinct keys present (at most 64, in practice the handful of experts); across the round's chunks an exclusive prefix per expert over
-    // the table; across rounds the running pos[].
+    // the table; across rounds the running pos[].  The table holds counts WITHIN the round only (16 bits: at most CMAX * 64 = 1024): the rows of earlier rounds, pos[e], are
+    // added as an int at placement — an expert may hold more than 65535 rows.
     int CH = WTAB / (ne > 0 ? ne : 1); CH = CH > CMAX ? CMAX : (CH < NW ? NW : CH & ~(NW - 1));
     const bool one_round = n_pairs <= CH * 64;
     const uint64_t lt = ln ? (~0ull >> (64 - ln)) : 0ull;                 // lanes below this one
-    // ranks the round's pairs inside their chunks (-> ekey / erank / esrc, per-chunk totals -> wtab), then turns the table into exclusive prefixes per expert started at start[e]
-    // (null: zero) and leaves the running totals in total[e]
-    auto rank_round = [&](int base, const int *start, int *total) __attribute__((always_inline)) {
+    // ranks the round's pairs inside their chunks (-> ekey / erank / esrc, per-chunk totals -> wtab), then turns the table into exclusive prefixes per expert within the
+    // round and leaves the round's totals in total[e]
+    auto rank_round = [&](int base, auto *total) __attribute__((always_inline)) {
         for (int i = tid; i < CH * ne; i += NT) wtab[i] = 0;
         // the round's ids: all of a thread's loads in flight together (this loop IS unrolled: rolled, every chunk paid a memory round trip of its own — 4 of the
         // planner's first 12 us); chunk c = NW i + wave is pairs base + NT i + tid
@@ -336,13 +338,13 @@ __device__ void moe_sk_plan(const moe_sk_args &a) {
         __syncthreads();
 #pragma unroll 1
         for (int e = tid; e < ne; e += NT) {
-            int run = start ? start[e] : 0;
+            int run = 0;
             for (int c = 0; c < CH; c++) { const int v = wtab[c * ne + e]; wtab[c * ne + e] = (uint16_t)run; run += v; }
-            total[e] = run;
+            total[e] = run;                                               // (a round's total fits 16 bits)
         }
         __syncthreads();
     };
-    if (one_round) rank_round(0, nullptr, cnt);                          // (the totals ARE the counts: no separate counting pass)
+    if (one_round) rank_round(0, cnt);                                   // (the totals ARE the counts: no separate counting pass)
     else {
         for (int e = tid; e < ne; e += NT) cnt[e] = 0;
         __syncthreads();
@@ -366,23 +368,25 @@ __device__ void moe_sk_plan(const moe_sk_args &a) {
     }
     __syncthreads();
     block_excl_scan<NT>(cpre, ntl, tmp);
-    auto place_round = [&](int base) __attribute__((always_inline)) {
+    // (start: the rows of every expert placed by earlier rounds, null: none)
+    auto place_round = [&](int base, const int *start) __attribute__((always_inline)) {
 #pragma unroll 1
         for (int i = tid; i < CH * 64; i += NT) {
             const int e = ekey[i];
             if (e < 0) continue;
-            const int rank = (int)wtab[(i >> 6) * ne + e] + (int)erank[i], t = tpre[e] + (rank >> trs), row = rank & (TR - 1);
+            const int rank = (start ? start[e] : 0) + (int)wtab[(i >> 6) * ne + e] + (int)erank[i], t = tpre[e] + (rank >> trs), row = rank & (TR - 1);
             if (t < ntl) { int32_t *rec = a.tile_rec + (int64_t)t * REC; rec[4 + row] = esrc[i]; rec[4 + TR + row] = base + i; }
         }
     };
-    if (one_round) place_round(0);
+    if (one_round) place_round(0, nullptr);
     else {
         for (int e = tid; e < ne; e += NT) pos[e] = 0;
 #pragma unroll 1
         for (int base = 0; base < n_pairs; base += CH * 64) {
-            rank_round(base, pos, pos);                                  // (its first barrier also orders pos[] = 0 / the previous round's placement in front of this round)
-            place_round(base);
+            rank_round(base, rtot);                                      // (its barriers also order pos[] = 0 / the previous round's update of pos[] in front of this round's placement)
+            place_round(base, pos);
             __syncthreads();
+            for (int e = tid; e < ne; e += NT) pos[e] += rtot[e];          // (read again two barriers on, in the next round's placement)
         }
     }
     // tile headers (the GEMM treats the entries behind a tile's rows as padding itself: they are never written)

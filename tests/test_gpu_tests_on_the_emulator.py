@@ -70,6 +70,13 @@ SELECTION_R3.append(("test_gpu_act_share.py", "(test_second_product and 16) or t
 SELECTION_R3.append(("test_gpu_group.py", "(ms2 and (12 or 2 or 14)) or refuses", 6))
 # ... and the second MUL_MAT_ID of one (b, ids) on the first one's front (ggml_cdna4_mul_mat_id_prepared): bit-identical to the full call; other routes leave no front
 SELECTION_R3.append(("test_gpu_moe_front.py", "4-2-True-96 or 8-2-False-40 or other_routes", 3))
+# the stream-k MUL_MAT_ID's planner beyond one round and its skewed jobs (tests/test_gpu_moe_plan.py), the smallest row of each: 1025 pairs of 8 experts (two rounds, the last
+# one pair long; 6 s here), 1024 experts (256-pair rounds, three; 28 s), 1100 pairs to expert 0 (5 s), no valid id at all (7 s) ...
+SELECTION_R3.append(("test_gpu_moe_plan.py", "(several_rounds and 1025 and not holes) or 1024-1-700 or (one_expert and q4_K-0) or no_valid_id", 4))
+# ... and k_gemm_kq_sk's window of eight tile records in LDS: spans of ten tiles (EMU_CUS=4 stands in for CDNA4_SK_SPANS; 15 s), a cut tile behind a reload (EMU_CUS=3; 31 s).
+# (The 65536-row expert is left to the GPU: ~4,100 quantizer work-groups and 516 tiles, each emulated work-group a process.)
+SELECTION_R3.append(("test_gpu_moe_plan.py", "record_window and 256-4", 1, {"EMU_CUS": "4"}))
+SELECTION_R3.append(("test_gpu_moe_plan.py", "record_window and 768-3", 1, {"EMU_CUS": "3"}))
 
 
 def _merged(selections):
