@@ -55,6 +55,11 @@ def _headers():
     return hs
 
 
+def _kernel_headers():
+    """headers only the kernel library's sources include (.hpp): outside the plug-in's digest, which _headers() feeds"""
+    return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
+
+
 def build_kernels(force=False, verbose=False):
     os.makedirs(LIB, exist_ok=True)
     os.makedirs(OBJ, exist_ok=True)
@@ -64,7 +69,7 @@ def build_kernels(force=False, verbose=False):
         src = os.path.join(CSRC, s)
         obj = os.path.join(OBJ, s.replace("/", "_") + ".o")
         objs.append(obj)
-        if force or _newer([src] + _headers(), obj):
+        if force or _newer([src] + _headers() + _kernel_headers(), obj):
             jobs.append([HIPCC] + HIPFLAGS + ["-c", src, "-o", obj])
     if jobs:
         if verbose:

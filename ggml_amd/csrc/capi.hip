@@ -1,6 +1,7 @@
 // capi.hip — the C-ABI of libcdna4_kernels.so (declared in include/ggml_cdna4.h).
 #include "../../include/ggml_cdna4.h"
 #include "cdna4_common.h"
+#include "cdna4_formats.hpp"
 #include "cdna4_kernels.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -17,16 +18,15 @@ int cdna4_set_error_msg(const char *msg) { snprintf(g_err, sizeof g_err, "%s", m
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // Q5_0 / Q3_K / Q2_K: int8-dot GEMV units of gemv_q.hip for up to 8 activation rows, above that the Q8_0 / Q6_K MFMA GEMM on an exact
 // re-encoding of the weights (convert_w.hip; Q2_K as [scale part | minimum part] against a doubled activation image)
-static inline bool is_kq(int t) { return t == CDNA4_Q4_K || t == CDNA4_Q5_K || t == CDNA4_Q6_K || t == CDNA4_Q2_K || t == CDNA4_Q3_K || t == CDNA4_IQ4_XS; }
 // Q4_1 / Q5_1 (Q8_1 activations: s in the place of the bsums) and IQ4_NL: GEMV units; above 8 rows the Q8_0 GEMM on the re-encoding
 // (Q4_1 / Q5_1 as [d q | m 1] against a doubled activation image, like Q2_K)
-static inline bool is_q(int t) { return is_kq(t) || t == CDNA4_Q4_0 || t == CDNA4_Q8_0 || t == CDNA4_Q5_0 || t == CDNA4_Q4_1 || t == CDNA4_Q5_1 || t == CDNA4_IQ4_NL; }
+// (which types these are: cdna4_common.h — cdna4_type_qk() != 0 for the twelve accepted weight formats, cdna4_type_is_kq() for their superblock half)
 
 // workspace carve: [qs int8 B*K][d f32 B*K/qka][bsums i16 B*K/16][xh f16 B*K]
 struct ws_view { int8_t *qs; float *d; int16_t *bsums; void *xh; size_t total; };
 static ws_view carve(int type, int64_t K, int64_t B, void *base) {
     ws_view v; uint8_t *p = (uint8_t *)base; size_t off = 0;
-    const int64_t qka = is_kq(type) ? 256 : 32;
+    const int64_t qka = cdna4_type_is_kq(type) ? 256 : 32;
     v.qs = (int8_t *)(p + off); off += align256((size_t)(B * K));
     v.d = (float *)(p + off); off += align256((size_t)(B * (K / qka)) * 4);
     v.bsums = (int16_t *)(p + off); off += align256((size_t)(B * (K / 16)) * 2);
@@ -115,26 +115,19 @@ int ggml_cdna4_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipS
 int ggml_cdna4_set_device(int device) { hipError_t e = hipSetDevice(device); return e == hipSuccess ? 0 : cdna4_set_error(e, __FILE__, __LINE__); }
 
 size_t ggml_cdna4_row_size(int type, int64_t k) {
-    switch (type) {
-        case CDNA4_F32: return (size_t)k * 4; case CDNA4_F16: return (size_t)k * 2;
-        case CDNA4_Q4_0: return k % 32 ? 0 : (size_t)(k / 32) * 18; case CDNA4_Q8_0: return k % 32 ? 0 : (size_t)(k / 32) * 34;
-        case CDNA4_Q4_K: return k % 256 ? 0 : (size_t)(k / 256) * 144; case CDNA4_Q5_K: return k % 256 ? 0 : (size_t)(k / 256) * 176;
-        case CDNA4_Q6_K: return k % 256 ? 0 : (size_t)(k / 256) * 210;
-        case CDNA4_Q5_0: return k % 32 ? 0 : (size_t)(k / 32) * 22; case CDNA4_Q2_K: return k % 256 ? 0 : (size_t)(k / 256) * 84;
-        case CDNA4_Q3_K: return k % 256 ? 0 : (size_t)(k / 256) * 110;
-        case CDNA4_Q4_1: return k % 32 ? 0 : (size_t)(k / 32) * 20; case CDNA4_Q5_1: return k % 32 ? 0 : (size_t)(k / 32) * 24;
-        case CDNA4_IQ4_NL: return k % 32 ? 0 : (size_t)(k / 32) * 18; case CDNA4_IQ4_XS: return k % 256 ? 0 : (size_t)(k / 256) * 136;
-    }
-    return 0;
+    if (type == CDNA4_F32) return (size_t)k * 4;
+    if (type == CDNA4_F16) return (size_t)k * 2;
+    const int qk = cdna4_type_qk(type);
+    return qk && k % qk == 0 ? (size_t)(k / qk) * cdna4_type_bytes(type) : 0;
 }
 
 size_t ggml_cdna4_mul_mat_workspace_size(int type, int64_t K, int64_t n_act_rows) {
-    if (!is_q(type) || K <= 0 || n_act_rows <= 0) return 0;
+    if (!cdna4_type_qk(type) || K <= 0 || n_act_rows <= 0) return 0;
     return carve(type, K, n_act_rows, nullptr).total;
 }
 
 size_t ggml_cdna4_mul_mat_id_workspace_size(int type, int64_t K, int64_t n_expert, int64_t n_used, int64_t n_b, int64_t n_tok) {
-    if (!is_q(type) || K <= 0 || n_tok <= 0 || n_used <= 0 || n_b <= 0 || n_expert <= 0) return 0;
+    if (!cdna4_type_qk(type) || K <= 0 || n_tok <= 0 || n_used <= 0 || n_b <= 0 || n_expert <= 0) return 0;
     const size_t plain = carve(type, K, n_tok * n_b, nullptr).total;
     if (!cdna4_gemm_ids_supported(type, K) || n_tok * n_used <= 32) return plain;
     size_t grouped = moe_carve(K, n_expert, n_used, n_tok, nullptr).total;
@@ -252,13 +245,13 @@ static bool use_mmq(int type, int64_t M, int64_t K, int64_t B) {
 }
 
 int ggml_cdna4_prepare_act(int type, const float *X, int64_t x_row_stride, int64_t K, int64_t B, void *workspace, size_t workspace_bytes, int path, void *stream) {
-    if (!is_q(type)) return cdna4_set_error_msg("prepare_act: unsupported weight type");
+    if (!cdna4_type_qk(type)) return cdna4_set_error_msg("prepare_act: unsupported weight type");
     if (B <= 0 || K <= 0) return 0;
     if (!workspace || ((uintptr_t)workspace & 255)) return cdna4_set_error_msg("prepare_act: workspace must be 256-byte aligned");
     const ws_view v = carve(type, K, B, workspace);
     if (workspace_bytes < v.total) return cdna4_set_error_msg("prepare_act: workspace too small");
     const bool want_i8 = path != GGML_CDNA4_PATH_GEMM, want_h = path != GGML_CDNA4_PATH_GEMV;
-    if (is_kq(type)) {
+    if (cdna4_type_is_kq(type)) {
         const int rc = ggml_cdna4_quantize_q8_K(X, x_row_stride, K, B, want_i8 ? v.qs : nullptr, v.d, v.bsums, want_h ? v.xh : nullptr, stream);
         if (rc || !want_h || cdna4_convert_weights_kmul(type) == 1) return rc;
         // the image is k-panel-major ([K / 128][B][128] fp16): k-panels K / 128 .. 2 K / 128 - 1 of the doubled image are a copy of the first B K halves
@@ -315,7 +308,7 @@ struct mm_plan {
 static mm_plan plan_mul_mat(int type, const void *W, int64_t w_row_bytes, const float *X, int64_t x_row_stride, int64_t M, int64_t K, int64_t B,
                             int path, int gemm_variant, int splitk, const void *workspace) {
     mm_plan p = {MM_NONE, 0, 0, true, -1};
-    if (!is_q(type) || M <= 0 || B <= 0 || K <= 0 || ggml_cdna4_row_size(type, K) == 0) return p;
+    if (!cdna4_type_qk(type) || M <= 0 || B <= 0 || K <= 0 || ggml_cdna4_row_size(type, K) == 0) return p;
     const bool autop = path == GGML_CDNA4_PATH_AUTO;
     // Formats with an exact same-shape re-encoding (Q5_0 / IQ4_NL -> Q8_0, Q3_K -> Q6_K) follow their TARGET format onto the int8 matrix-core kernel
     // where that one is chosen: its integer dots on Q8_0 activations are the CPU's own arithmetic for the source format (tests/test_gpu_widening.py).
@@ -334,7 +327,7 @@ static mm_plan plan_mul_mat(int type, const void *W, int64_t w_row_bytes, const 
         if (!autop) return p;
         gemm = false;
     }
-    const uint32_t key = 1u | (is_kq(type) ? 2u : 0u) | (cdna4_is_q81(type) ? 4u : 0u) | (kmul == 2 ? 8u : 0u);
+    const uint32_t key = 1u | (cdna4_type_is_kq(type) ? 2u : 0u) | (cdna4_is_q81(type) ? 4u : 0u) | (kmul == 2 ? 8u : 0u);
     if (!gemm) {                                                          // the integer-dot family: the tail rides in the store
         // one launch while the redundant per-work-group quantization is cheap: B x K up to 32 K values, B rounded to the instantiated 2 / 4 / 8 columns
         const int64_t nbt = B <= 1 ? 1 : (B <= 2 ? 2 : (B <= 4 ? 4 : 8));
@@ -367,7 +360,7 @@ static int mul_mat_impl(int type, const void *W, int64_t w_row_bytes, const floa
                         int64_t M, int64_t K, int64_t B, void *workspace, size_t workspace_bytes, int path, int gemm_variant, int splitk,
                         const cdna4_epilogue &epi, void *stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (!is_q(type)) return cdna4_set_error_msg("mul_mat: unsupported weight type");
+    if (!cdna4_type_qk(type)) return cdna4_set_error_msg("mul_mat: unsupported weight type");
     if (M <= 0 || B <= 0) return 0;
     if (K <= 0 || ggml_cdna4_row_size(type, K) == 0) return cdna4_set_error_msg("mul_mat: K is not a whole number of blocks");
     const mm_plan p = plan_mul_mat(type, W, w_row_bytes, X, x_row_stride, M, K, B, path, gemm_variant, splitk, workspace);
@@ -428,7 +421,7 @@ int ggml_cdna4_mul_mat_group(int type, int n, const void *const *W, const int64_
     if (const int frc = fault_status()) return frc;
     const char *why = nullptr;
     if (n < 1 || n > CDNA4_GEMV_GROUP_MAX || !W || !w_row_bytes || !M || !Y || !X) why = "mul_mat_group: 1 .. 4 matrices";
-    else if (!(type == CDNA4_Q4_K || type == CDNA4_Q5_K || type == CDNA4_Q6_K || type == CDNA4_Q4_0 || type == CDNA4_Q8_0)) why = "mul_mat_group: no grouped form for this type";
+    else if (!cdna4_type_is_main5(type)) why = "mul_mat_group: no grouped form for this type";
     cdna4_gemv_group g{};
     g.K = (int)K;
     for (int i = 0; i < n && !why; i++) {
@@ -493,13 +486,13 @@ static int norm_affine_act(const ggml_cdna4_tensor *src0, const ggml_cdna4_tenso
                            int type, void *workspace, size_t workspace_bytes, void *stream, bool kq);
 int ggml_cdna4_op_norm_affine_q8_K(const ggml_cdna4_tensor *src0, const ggml_cdna4_tensor *gain, const ggml_cdna4_tensor *shift, const ggml_cdna4_tensor *dst, float eps, int rms,
                                    int type, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!is_q(type) || !is_kq(type) || cdna4_convert_weights_kmul(type) != 1) return cdna4_set_error_msg("norm_q8_K: the image is the K-quants' (Q8_K activations, single image)");
+    if (!cdna4_type_is_kq(type) || cdna4_convert_weights_kmul(type) != 1) return cdna4_set_error_msg("norm_q8_K: the image is the K-quants' (Q8_K activations, single image)");
     return norm_affine_act(src0, gain, shift, dst, eps, rms, type, workspace, workspace_bytes, stream, true);
 }
 // the same for the 32-block formats whose activations are Q8_0 (Q4_0 / Q8_0 / Q5_0 / IQ4_NL; ggml_cdna4_act_image_key == 17): the image of k_quantize_q8_0, bit for bit
 int ggml_cdna4_op_norm_affine_q8_0(const ggml_cdna4_tensor *src0, const ggml_cdna4_tensor *gain, const ggml_cdna4_tensor *shift, const ggml_cdna4_tensor *dst, float eps, int rms,
                                    int type, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!is_q(type) || is_kq(type) || cdna4_is_q81(type) || cdna4_convert_weights_kmul(type) != 1) return cdna4_set_error_msg("norm_q8_0: the image is the 32-block formats' (Q8_0 activations, single image)");
+    if (!cdna4_type_qk(type) || cdna4_type_is_kq(type) || cdna4_is_q81(type) || cdna4_convert_weights_kmul(type) != 1) return cdna4_set_error_msg("norm_q8_0: the image is the 32-block formats' (Q8_0 activations, single image)");
     return norm_affine_act(src0, gain, shift, dst, eps, rms, type, workspace, workspace_bytes, stream, false);
 }
 static int norm_affine_act(const ggml_cdna4_tensor *src0, const ggml_cdna4_tensor *gain, const ggml_cdna4_tensor *shift, const ggml_cdna4_tensor *dst, float eps, int rms,
@@ -562,7 +555,7 @@ int ggml_cdna4_mul_mat_id(int type, const void *as, int64_t w_row_bytes, int64_t
 // ggml_cdna4_mul_mat_id_prepared with other expert weights of the same type / M / K, the same b, ids, strides and counts, on the untouched workspace multiplies it again
 // (ONE launch instead of two, bit-identical to the full call).
 uint32_t ggml_cdna4_mul_mat_id_front_key(int type, const void *as, int64_t w_row_bytes, int64_t w_expert_bytes, int64_t M, int64_t K, int64_t n_expert, int64_t n_used, int64_t n_b, int64_t n_tok, size_t workspace_bytes) {
-    if (!is_q(type) || M <= 0 || K <= 0 || n_tok <= 0 || n_used <= 0 || n_b <= 0 || n_used % n_b || ggml_cdna4_row_size(type, K) == 0) return 0;
+    if (!cdna4_type_qk(type) || M <= 0 || K <= 0 || n_tok <= 0 || n_used <= 0 || n_b <= 0 || n_used % n_b || ggml_cdna4_row_size(type, K) == 0) return 0;
     if (!(cdna4_gemm_ids_supported(type, K) && n_tok * n_used > 32 && n_expert <= 1024) || (((uintptr_t)as | (uintptr_t)w_row_bytes | (uintptr_t)w_expert_bytes) & 1)) return 0;
     const moe_sk_pick pk = moe_sk_pick_of(type, as, w_row_bytes, w_expert_bytes, M, K, n_expert, n_used, n_b, n_tok);
     if (pk.type < 0 || workspace_bytes < moe_sk_carve(K, n_expert, n_used, n_b, n_tok, nullptr).total) return 0;
@@ -581,7 +574,7 @@ static int mul_mat_id_impl(bool front_in_place, int type, const void *as, int64_
                            int64_t M, int64_t K, int64_t n_expert, int64_t n_used, int64_t n_b, int64_t n_tok,
                            void *workspace, size_t workspace_bytes, void *stream) {
     if (const int frc = fault_status()) return frc;
-    if (!is_q(type)) return cdna4_set_error_msg("mul_mat_id: unsupported weight type");
+    if (!cdna4_type_qk(type)) return cdna4_set_error_msg("mul_mat_id: unsupported weight type");
     if (M <= 0 || n_tok <= 0 || n_used <= 0) return 0;
     if (K <= 0 || ggml_cdna4_row_size(type, K) == 0) return cdna4_set_error_msg("mul_mat_id: K is not a whole number of blocks");
     if (n_b <= 0 || n_used % n_b) return cdna4_set_error_msg("mul_mat_id: n_used must be a multiple of b.ne[1]");   // ggml_mul_mat_id: ids->ne[0] % b->ne[1] == 0 (src/ggml.c:2747); slot u reads row u % n_b
@@ -634,14 +627,14 @@ static int mul_mat_id_impl(bool front_in_place, int type, const void *as, int64_
                 iv.qs = (int8_t *)mv.xh;
                 iv.d = (float *)((uint8_t *)mv.xh + align256((size_t)mv.img_rows * K));
                 int16_t *ibs = (int16_t *)((uint8_t *)iv.d + align256((size_t)mv.img_rows * (K / 32) * 4));
-                rc = is_kq(type) ? cdna4_launch_quantize_q8_K_gather_i8(b, b_row_stride, K, mv.img_rows, mv.img_src, iv.qs, iv.d, ibs, (hipStream_t)stream)
+                rc = cdna4_type_is_kq(type) ? cdna4_launch_quantize_q8_K_gather_i8(b, b_row_stride, K, mv.img_rows, mv.img_src, iv.qs, iv.d, ibs, (hipStream_t)stream)
                                  : cdna4_launch_quantize_q8_0_gather_i8(b, b_row_stride, K, mv.img_rows, mv.img_src, iv.qs, iv.d, (hipStream_t)stream);
                 if (rc) return rc;
-                iv.bsums = is_kq(type) ? ibs : nullptr;
+                iv.bsums = cdna4_type_is_kq(type) ? ibs : nullptr;
                 const cdna4_gemv_args g = gemv_args_of(type, as, w_row_bytes, iv, dst, dst_row_stride, M, K, mv.img_rows, cdna4_epilogue{});
                 return cdna4_launch_mmq_ids(g, mv.tile_expert, mv.img_dst, w_expert_bytes, (hipStream_t)stream);
             }
-            rc = is_kq(type) ? cdna4_launch_quantize_q8_K_gather(b, b_row_stride, K, mv.img_rows, mv.img_src, mv.xh, (hipStream_t)stream)
+            rc = cdna4_type_is_kq(type) ? cdna4_launch_quantize_q8_K_gather(b, b_row_stride, K, mv.img_rows, mv.img_src, mv.xh, (hipStream_t)stream)
                              : cdna4_launch_quantize_q8_0_gather(b, b_row_stride, K, mv.img_rows, mv.img_src, mv.xh, (hipStream_t)stream);
             if (rc) return rc;
             cdna4_gemm_args a = gemm_args_of(type, as, w_row_bytes, mv.xh, dst, dst_row_stride, M, K, mv.img_rows, 0, 0, cdna4_epilogue{});

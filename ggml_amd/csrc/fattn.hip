@@ -27,6 +27,7 @@
 //                       dimension) and shared through LDS: 2 + hs / 16 ... MFMAs per wave and chunk instead of 3 hs / 16.
 #include "../../include/ggml_cdna4.h"
 #include "cdna4_common.h"
+#include "cdna4_formats.hpp"
 #include "cdna4_kernels.h"
 #include "gemm_q_hw.h"
 #include <math.h>
@@ -1243,9 +1244,8 @@ static int fa_f16(const T4 *q, const T4 *k, const T4 *v, const T4 *mask, const T
             }
             const int xcd_map = getenv("CDNA4_FA_MAP") ? atoi(getenv("CDNA4_FA_MAP")) : (mask ? 1 : 0);     // (A/B knob; see the kernel)
             const int mode = (logit_softcap != 0.0f || !(p.scale > 0.0f) || (mask && !p.mask_vec)) ? 2 : (mask ? 1 : 0);
-#define FA_PIPE3(HS_, NW_, MODE_) do { constexpr int lds_ = k_flash_attn_pipe_lds<HS_, NW_, MODE_>(); static bool raised_ = false;                                \
-                if (lds_ > 64 * 1024 && !raised_) { if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_flash_attn_pipe<HS_, NW_, MODE_>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_) != hipSuccess) { \
-                    (void)hipGetLastError(); return cdna4_set_error_msg("flash_attn_ext: cannot raise the dynamic LDS limit"); } raised_ = true; }                \
+#define FA_PIPE3(HS_, NW_, MODE_) do { constexpr int lds_ = k_flash_attn_pipe_lds<HS_, NW_, MODE_>();                                                            \
+                if (lds_ > 64 * 1024) { if (const int rc_ = cdna4_raise_lds_limit<k_flash_attn_pipe<HS_, NW_, MODE_>>(lds_, "flash_attn_ext: cannot raise the dynamic LDS limit")) return rc_; } \
                 hipLaunchKernelGGL((k_flash_attn_pipe<HS_, NW_, MODE_>), dim3((unsigned)items), dim3(64 * NW_), lds_, st, p, (int)qtiles, xcd_map, flags); } while (0)
 #define FA_PIPE(HS_, NW_) do { if (mode == 0) FA_PIPE3(HS_, NW_, 0); else if (mode == 1) FA_PIPE3(HS_, NW_, 1); else FA_PIPE3(HS_, NW_, 2); } while (0)
             if (D == 64) { if (nw == 8) FA_PIPE(64, 8); else if (nw == 4) FA_PIPE(64, 4); else FA_PIPE(64, 2); }

@@ -21,6 +21,7 @@
 //    (huge grids: k_gemm_kq_t64<.., 256> of gemm_q_t64.hip)
 //    k_repack_*      16-byte-aligned re-layout of Q4_0 / Q8_0 / Q6_K into scratch (shallow-K fallback of the staged path)
 #include "gemm_q_common.h"
+#include "cdna4_formats.hpp"
 #include <atomic>
 #include <mutex>
 #include "gemm_q_hw.h"
@@ -699,21 +700,15 @@ static int launch_ids(const cdna4_gemm_args &a, const int32_t *tile_expert, cons
     return 0;
 }
 bool cdna4_gemm_ids_supported(int type, int64_t K) {
-    if (type == CDNA4_Q4_K || type == CDNA4_Q5_K || type == CDNA4_Q6_K) return K >= 256 && K % 256 == 0;
-    return (type == CDNA4_Q4_0 || type == CDNA4_Q8_0) && K >= 128 && K % 128 == 0;       // whole 128-k panels of the image, whole 64-k slices
+    const int64_t unit = cdna4_type_is_kq(type) ? 256 : 128;                              // (32-weight formats: whole 128-k panels of the image, whole 64-k slices)
+    return cdna4_type_is_main5(type) && K >= unit && K % unit == 0;
 }
 int cdna4_launch_gemm_ids(const cdna4_gemm_args &a, const int32_t *tile_expert, const int32_t *row_dst, int64_t w_expert_bytes, hipStream_t st) {
     if (!cdna4_gemm_ids_supported(a.type, a.K) || a.B % 128) return cdna4_set_error_msg("gemm_ids: unsupported type / K, or image rows not a multiple of 128");
     if (((uintptr_t)a.xh & 15) || (((uintptr_t)a.W | (uintptr_t)a.w_row_bytes | (uintptr_t)w_expert_bytes) & 1)) return cdna4_set_error_msg("gemm_ids: misaligned operands");
-    switch (a.type) {
-        case CDNA4_Q4_K:
-            if (!(((uintptr_t)a.W | (uintptr_t)a.w_row_bytes | (uintptr_t)w_expert_bytes) & 15)) return cdna4_launch_gemm_t64_ids(a, tile_expert, row_dst, w_expert_bytes, st);
-            return launch_ids<CDNA4_Q4_K>(a, tile_expert, row_dst, w_expert_bytes, st);
-        case CDNA4_Q5_K: return launch_ids<CDNA4_Q5_K>(a, tile_expert, row_dst, w_expert_bytes, st);
-        case CDNA4_Q6_K: return launch_ids<CDNA4_Q6_K>(a, tile_expert, row_dst, w_expert_bytes, st);
-        case CDNA4_Q4_0: return launch_ids<CDNA4_Q4_0>(a, tile_expert, row_dst, w_expert_bytes, st);
-        case CDNA4_Q8_0: return launch_ids<CDNA4_Q8_0>(a, tile_expert, row_dst, w_expert_bytes, st);
-    }
+    if (a.type == CDNA4_Q4_K && !(((uintptr_t)a.W | (uintptr_t)a.w_row_bytes | (uintptr_t)w_expert_bytes) & 15)) return cdna4_launch_gemm_t64_ids(a, tile_expert, row_dst, w_expert_bytes, st);
+    int rc = 0;
+    if (cdna4_dispatch(cdna4_main5{}, a.type, [&](auto t) { rc = launch_ids<t.value>(a, tile_expert, row_dst, w_expert_bytes, st); })) return rc;
     return cdna4_set_error_msg("gemm_ids: unsupported weight type");
 }
 
@@ -778,12 +773,7 @@ int cdna4_launch_gemm_q(const cdna4_gemm_args &a, hipStream_t st) {
         ROUTE_END_K(true, 12);
         return cdna4_launch_gemm_lds(a, 256, a.splitk, st, 2);
     }
-    switch (a.type) {
-        case CDNA4_Q4_K: return launch_type<CDNA4_Q4_K>(a, st);
-        case CDNA4_Q5_K: return launch_type<CDNA4_Q5_K>(a, st);
-        case CDNA4_Q6_K: return launch_type<CDNA4_Q6_K>(a, st);
-        case CDNA4_Q4_0: return launch_type<CDNA4_Q4_0>(a, st);
-        case CDNA4_Q8_0: return launch_type<CDNA4_Q8_0>(a, st);
-    }
+    int rc = 0;
+    if (cdna4_dispatch(cdna4_main5{}, a.type, [&](auto t) { rc = launch_type<t.value>(a, st); })) return rc;
     return cdna4_set_error_msg("gemm_q: unsupported weight type");
 }

@@ -9,6 +9,7 @@
 // bytes are in flight before the first v_dot4_i32_i8; 64-lane butterfly reduction at the end.
 // Also serves MUL_MAT_ID (per-column expert base, ids read on the device — no host sync).
 #include "cdna4_common.h"
+#include "cdna4_formats.hpp"
 #include "cdna4_kernels.h"
 #include "quantize_dev.h"
 #include "epilogue.h"
@@ -765,8 +766,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_q_fused_grp(const cdna4_gemv_g
 }
 
 size_t cdna4_gemv_fused_lds_bytes(int type, int64_t K) {
-    const bool kq = type == CDNA4_Q4_K || type == CDNA4_Q5_K || type == CDNA4_Q6_K || type == CDNA4_Q2_K || type == CDNA4_Q3_K || type == CDNA4_IQ4_XS;
-    return (size_t)(K + (kq ? K / 8 + (K / 256) * 4 : (K / 32) * 4) + (cdna4_is_q81(type) ? K / 8 : 0));
+    return (size_t)(K + (cdna4_type_is_kq(type) ? K / 8 + (K / 256) * 4 : (K / 32) * 4) + (cdna4_is_q81(type) ? K / 8 : 0));
 }
 static int fused_nb(int64_t B) { return B <= 1 ? 1 : (B <= 2 ? 2 : (B <= 4 ? 4 : 8)); }      // instantiated column counts
 bool cdna4_gemv_fused_supported(int type, int64_t K, int64_t B) {
@@ -776,8 +776,7 @@ bool cdna4_gemv_fused_supported(int type, int64_t K, int64_t B) {
     // 512 — on the row's scales.  Found by the CPU emulation of the whole library (K = 544); such K take the quantize + GEMV pair instead.
     if (K % 64) return false;
     if (B == 1) return cdna4_gemv_fused_lds_bytes(type, K) <= 64 * 1024;
-    const bool main5 = type == CDNA4_Q4_K || type == CDNA4_Q5_K || type == CDNA4_Q6_K || type == CDNA4_Q4_0 || type == CDNA4_Q8_0;
-    return main5 && (size_t)fused_nb(B) * cdna4_gemv_fused_lds_bytes(type, K) <= 150 * 1024;
+    return cdna4_type_is_main5(type) && (size_t)fused_nb(B) * cdna4_gemv_fused_lds_bytes(type, K) <= 150 * 1024;
 }
 template <int TYPE>
 static int launch_fused(const cdna4_gemv_args &a, const float *x, hipStream_t st) {
@@ -816,20 +815,15 @@ static int launch_fused(const cdna4_gemv_args &a, const float *x, hipStream_t st
 template <int TYPE, int NB>
 static int launch_fused_nb(const cdna4_gemv_args &a, const float *x, int64_t x_row_stride, hipStream_t st) {
     const size_t lds = (size_t)NB * cdna4_gemv_fused_lds_bytes(TYPE, a.K);
-    static bool raised_[16] = {};                                       // (a function attribute is per device)
-    int dev_ = 0; if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= 16) { (void)hipGetLastError(); dev_ = 0; }
-    bool &raised = raised_[dev_];
-    if (!raised) {
-        if (hipFuncSetAttribute((const void *)k_gemv_q_fused<TYPE, 8, 2, false, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) { (void)hipGetLastError(); return cdna4_set_error_msg("gemv_q_fused: cannot raise the dynamic LDS limit"); }
-        if constexpr (NB <= 4 && (QT<TYPE>::KQ || TYPE == CDNA4_Q4_0) && !(TYPE == CDNA4_Q5_K && NB == 2)) {      // (Q5_K x 2 columns needs more than the 128 registers of a 16-wave work-group)
-            if (hipFuncSetAttribute((const void *)k_gemv_q_fused<TYPE, 16, 1, false, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) { (void)hipGetLastError(); return cdna4_set_error_msg("gemv_q_fused: cannot raise the dynamic LDS limit"); }
-        }
-        raised = true;
-    }
+    constexpr bool HAS16 = NB <= 4 && (QT<TYPE>::KQ || TYPE == CDNA4_Q4_0) && !(TYPE == CDNA4_Q5_K && NB == 2);      // (Q5_K x 2 columns needs more than the 128 registers of a 16-wave work-group)
+    int rc;
+    if constexpr (HAS16) rc = cdna4_raise_lds_limit<k_gemv_q_fused<TYPE, 8, 2, false, NB>, k_gemv_q_fused<TYPE, 16, 1, false, NB>>(150 * 1024, "gemv_q_fused: cannot raise the dynamic LDS limit");
+    else rc = cdna4_raise_lds_limit<k_gemv_q_fused<TYPE, 8, 2, false, NB>>(150 * 1024, "gemv_q_fused: cannot raise the dynamic LDS limit");
+    if (rc) return rc;
     // Round 6: 2 and 4 rows take the 16-wave x 1-row work-groups of the one-row decode (round 5: the quantizer is still paid once per 16 weight rows, by twice as many
     // lanes, and every wave multiplies ONE row) wherever that is one work-group per CU at most — CDNA4_FUSED_NB_CFG=0 keeps 8 x 2
     static const int cfg_env = getenv("CDNA4_FUSED_NB_CFG") ? atoi(getenv("CDNA4_FUSED_NB_CFG")) : -1;
-    if constexpr (NB <= 4 && (QT<TYPE>::KQ || TYPE == CDNA4_Q4_0) && !(TYPE == CDNA4_Q5_K && NB == 2)) {      // (Q5_K x 2 columns needs more than the 128 registers of a 16-wave work-group)
+    if constexpr (HAS16) {
         if (cfg_env != 0 && (a.M + 15) / 16 <= cdna4_gemm_cu_count() && a.M >= 2048) {
             hipLaunchKernelGGL((k_gemv_q_fused<TYPE, 16, 1, false, NB>), dim3((a.M + 15) / 16), dim3(1024), lds, st, a, x, x_row_stride);
             CDNA4_CHECK_LAUNCH();
@@ -847,10 +841,7 @@ static int launch_fused_n(const cdna4_gemv_args &a, const float *x, int64_t x_ro
 template <int TYPE, int NB>
 static int launch_staged_nb(const cdna4_gemv_args &a, hipStream_t st) {
     const size_t lds = (size_t)NB * cdna4_gemv_fused_lds_bytes(TYPE, a.K);
-    static bool raised_[16] = {};                                       // (a function attribute is per device)
-    int dev_ = 0; if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= 16) { (void)hipGetLastError(); dev_ = 0; }
-    bool &raised = raised_[dev_];
-    if (!raised) { if (hipFuncSetAttribute((const void *)k_gemv_q_fused<TYPE, 8, 2, false, NB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) { (void)hipGetLastError(); return cdna4_set_error_msg("gemv_q_staged: cannot raise the dynamic LDS limit"); } raised = true; }
+    if (const int rc = cdna4_raise_lds_limit<k_gemv_q_fused<TYPE, 8, 2, false, NB, true>>(150 * 1024, "gemv_q_staged: cannot raise the dynamic LDS limit")) return rc;
     hipLaunchKernelGGL((k_gemv_q_fused<TYPE, 8, 2, false, NB, true>), dim3((a.M + 15) / 16), dim3(512), lds, st, a, (const float *)nullptr, (int64_t)0);
     CDNA4_CHECK_LAUNCH();
     return 0;
@@ -859,23 +850,24 @@ template <int TYPE>
 static int launch_staged(const cdna4_gemv_args &a, hipStream_t st) {
     switch (fused_nb(a.ncol)) { case 2: return launch_staged_nb<TYPE, 2>(a, st); case 4: return launch_staged_nb<TYPE, 4>(a, st); default: return launch_staged_nb<TYPE, 8>(a, st); }
 }
+// the per-format operand checks of every entry point below: K a whole number of blocks; Q4_K / Q5_K rows (and expert matrices, where the call has them) 16-byte aligned
+// for the kernels' 16-byte loads.  0, or the error status
+static int gemv_operands_ok(int type, int64_t K, const void *W, int64_t w_row_bytes, int64_t w_expert_bytes = 0) {
+    if ((type == CDNA4_Q4_K || type == CDNA4_Q5_K) && (((uintptr_t)W | (uintptr_t)w_row_bytes | (uintptr_t)w_expert_bytes) & 15)) return cdna4_set_error_msg("gemv_q: Q4_K/Q5_K rows must be 16-byte aligned");
+    const int qk = cdna4_type_qk(type);
+    if (qk && K % qk) return cdna4_set_error_msg(qk == 32 ? "gemv_q: K must be a multiple of 32" : "gemv_q: K must be a multiple of 256");
+    return 0;
+}
 // 2..8 PRE-QUANTIZED activation rows (a.qs / a.d / a.bsums as ggml_cdna4_prepare_act lays them out), staged into LDS once per work-group
 bool cdna4_gemv_staged_supported(int type, int64_t K, int64_t B) {
-    const int64_t nqd = K / ((type == CDNA4_Q4_0 || type == CDNA4_Q8_0) ? 32 : 256);
-    return B >= 2 && cdna4_gemv_fused_supported(type, K, B) && K % 128 == 0 && nqd > 0;
+    return B >= 2 && cdna4_gemv_fused_supported(type, K, B) && K % 128 == 0 && K >= cdna4_type_qk(type);        // (at least one block of scales)
 }
 int cdna4_launch_gemv_q_staged(const cdna4_gemv_args &a, hipStream_t st) {
     if (a.M <= 0) return 0;
     if (!cdna4_gemv_staged_supported(a.type, a.K, a.ncol) || a.ids) return cdna4_set_error_msg("gemv_q_staged: unsupported shape");
     if (((uintptr_t)a.qs | (uintptr_t)a.bsums) & 15) return cdna4_set_error_msg("gemv_q_staged: quantized activations must be 16-byte aligned");
-    switch (a.type) {
-        case CDNA4_Q4_K: case CDNA4_Q5_K:
-            if (((uintptr_t)a.W | (uintptr_t)a.w_row_bytes) & 15) return cdna4_set_error_msg("gemv_q: Q4_K/Q5_K rows must be 16-byte aligned");
-            return a.type == CDNA4_Q4_K ? launch_staged<CDNA4_Q4_K>(a, st) : launch_staged<CDNA4_Q5_K>(a, st);
-        case CDNA4_Q6_K: return launch_staged<CDNA4_Q6_K>(a, st);
-        case CDNA4_Q4_0: return launch_staged<CDNA4_Q4_0>(a, st);
-        case CDNA4_Q8_0: return launch_staged<CDNA4_Q8_0>(a, st);
-    }
+    int rc = gemv_operands_ok(a.type, a.K, a.W, a.w_row_bytes);
+    if (rc || cdna4_dispatch(cdna4_main5{}, a.type, [&](auto t) { rc = launch_staged<t.value>(a, st); })) return rc;
     return cdna4_set_error_msg("gemv_q_staged: unsupported weight type");
 }
 // a.ncol = 2..8 rows of x (fp32, 16-byte aligned, x_row_stride elements apart), quantized in LDS; Y column c at a.Y + c * a.y_col_stride
@@ -884,15 +876,8 @@ int cdna4_launch_gemv_q_fused_n(const cdna4_gemv_args &a, const float *x, int64_
     if (a.ncol < 2 || !cdna4_gemv_fused_supported(a.type, a.K, a.ncol)) return cdna4_set_error_msg("gemv_q_fused_n: unsupported shape");
     if (((uintptr_t)x | (uintptr_t)(x_row_stride * 4)) & 15) return cdna4_set_error_msg("gemv_q_fused_n: x rows must be 16-byte aligned");
     if (((uintptr_t)a.W | (uintptr_t)a.w_row_bytes) & 1) return cdna4_set_error_msg("gemv_q: misaligned operands");
-    switch (a.type) {
-        case CDNA4_Q4_K: case CDNA4_Q5_K:
-            if (((uintptr_t)a.W | (uintptr_t)a.w_row_bytes) & 15) return cdna4_set_error_msg("gemv_q: Q4_K/Q5_K rows must be 16-byte aligned");
-            if (a.K % 256) return cdna4_set_error_msg("gemv_q: K must be a multiple of 256");
-            return a.type == CDNA4_Q4_K ? launch_fused_n<CDNA4_Q4_K>(a, x, x_row_stride, st) : launch_fused_n<CDNA4_Q5_K>(a, x, x_row_stride, st);
-        case CDNA4_Q6_K: if (a.K % 256) return cdna4_set_error_msg("gemv_q: K must be a multiple of 256"); return launch_fused_n<CDNA4_Q6_K>(a, x, x_row_stride, st);
-        case CDNA4_Q4_0: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_fused_n<CDNA4_Q4_0>(a, x, x_row_stride, st);
-        case CDNA4_Q8_0: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_fused_n<CDNA4_Q8_0>(a, x, x_row_stride, st);
-    }
+    int rc = gemv_operands_ok(a.type, a.K, a.W, a.w_row_bytes);
+    if (rc || cdna4_dispatch(cdna4_main5{}, a.type, [&](auto t) { rc = launch_fused_n<t.value>(a, x, x_row_stride, st); })) return rc;
     return cdna4_set_error_msg("gemv_q_fused_n: unsupported weight type");
 }
 
@@ -900,24 +885,8 @@ int cdna4_launch_gemv_q(const cdna4_gemv_args &a, hipStream_t st) {
     if (a.M <= 0 || a.ncol <= 0) return 0;
     if (((uintptr_t)a.W | (uintptr_t)a.w_row_bytes | (uintptr_t)a.qs) & 1) return cdna4_set_error_msg("gemv_q: misaligned operands");
     if (a.ids && a.ncol > 65535) return cdna4_set_error_msg("gemv_q: too many MUL_MAT_ID columns");
-    switch (a.type) {
-        case CDNA4_Q4_K: case CDNA4_Q5_K:
-            if (((uintptr_t)a.W | (uintptr_t)a.w_row_bytes | (uintptr_t)a.w_expert_bytes) & 15) return cdna4_set_error_msg("gemv_q: Q4_K/Q5_K rows must be 16-byte aligned");
-            if (a.K % 256) return cdna4_set_error_msg("gemv_q: K must be a multiple of 256");
-            return a.type == CDNA4_Q4_K ? launch_type<CDNA4_Q4_K>(a, st) : launch_type<CDNA4_Q5_K>(a, st);
-        case CDNA4_Q6_K:
-            if (a.K % 256) return cdna4_set_error_msg("gemv_q: K must be a multiple of 256");
-            return launch_type<CDNA4_Q6_K>(a, st);
-        case CDNA4_Q4_0: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_type<CDNA4_Q4_0>(a, st);
-        case CDNA4_Q8_0: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_type<CDNA4_Q8_0>(a, st);
-        case CDNA4_Q5_0: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_type<CDNA4_Q5_0>(a, st);
-        case CDNA4_Q4_1: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_type<CDNA4_Q4_1>(a, st);
-        case CDNA4_Q5_1: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_type<CDNA4_Q5_1>(a, st);
-        case CDNA4_IQ4_NL: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_type<CDNA4_IQ4_NL>(a, st);
-        case CDNA4_Q2_K: if (a.K % 256) return cdna4_set_error_msg("gemv_q: K must be a multiple of 256"); return launch_type<CDNA4_Q2_K>(a, st);
-        case CDNA4_Q3_K: if (a.K % 256) return cdna4_set_error_msg("gemv_q: K must be a multiple of 256"); return launch_type<CDNA4_Q3_K>(a, st);
-        case CDNA4_IQ4_XS: if (a.K % 256) return cdna4_set_error_msg("gemv_q: K must be a multiple of 256"); return launch_type<CDNA4_IQ4_XS>(a, st);
-    }
+    int rc = gemv_operands_ok(a.type, a.K, a.W, a.w_row_bytes, a.w_expert_bytes);
+    if (rc || cdna4_dispatch(cdna4_all12{}, a.type, [&](auto t) { rc = launch_type<t.value>(a, st); })) return rc;
     return cdna4_set_error_msg("gemv_q: unsupported weight type");
 }
 
@@ -927,24 +896,8 @@ int cdna4_launch_gemv_q_fused(const cdna4_gemv_args &a, const float *x, hipStrea
     if (!cdna4_gemv_fused_supported(a.type, a.K, a.ncol)) return cdna4_set_error_msg("gemv_q_fused: unsupported shape");
     if ((uintptr_t)x & 15) return cdna4_set_error_msg("gemv_q_fused: x must be 16-byte aligned");
     if (((uintptr_t)a.W | (uintptr_t)a.w_row_bytes) & 1) return cdna4_set_error_msg("gemv_q: misaligned operands");
-    switch (a.type) {
-        case CDNA4_Q4_K: case CDNA4_Q5_K:
-            if (((uintptr_t)a.W | (uintptr_t)a.w_row_bytes) & 15) return cdna4_set_error_msg("gemv_q: Q4_K/Q5_K rows must be 16-byte aligned");
-            if (a.K % 256) return cdna4_set_error_msg("gemv_q: K must be a multiple of 256");
-            return a.type == CDNA4_Q4_K ? launch_fused<CDNA4_Q4_K>(a, x, st) : launch_fused<CDNA4_Q5_K>(a, x, st);
-        case CDNA4_Q6_K:
-            if (a.K % 256) return cdna4_set_error_msg("gemv_q: K must be a multiple of 256");
-            return launch_fused<CDNA4_Q6_K>(a, x, st);
-        case CDNA4_Q4_0: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_fused<CDNA4_Q4_0>(a, x, st);
-        case CDNA4_Q8_0: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_fused<CDNA4_Q8_0>(a, x, st);
-        case CDNA4_Q5_0: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_fused<CDNA4_Q5_0>(a, x, st);
-        case CDNA4_Q4_1: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_fused<CDNA4_Q4_1>(a, x, st);
-        case CDNA4_Q5_1: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_fused<CDNA4_Q5_1>(a, x, st);
-        case CDNA4_IQ4_NL: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_fused<CDNA4_IQ4_NL>(a, x, st);
-        case CDNA4_Q2_K: if (a.K % 256) return cdna4_set_error_msg("gemv_q: K must be a multiple of 256"); return launch_fused<CDNA4_Q2_K>(a, x, st);
-        case CDNA4_Q3_K: if (a.K % 256) return cdna4_set_error_msg("gemv_q: K must be a multiple of 256"); return launch_fused<CDNA4_Q3_K>(a, x, st);
-        case CDNA4_IQ4_XS: if (a.K % 256) return cdna4_set_error_msg("gemv_q: K must be a multiple of 256"); return launch_fused<CDNA4_IQ4_XS>(a, x, st);
-    }
+    int rc = gemv_operands_ok(a.type, a.K, a.W, a.w_row_bytes);
+    if (rc || cdna4_dispatch(cdna4_all12{}, a.type, [&](auto t) { rc = launch_fused<t.value>(a, x, st); })) return rc;
     return cdna4_set_error_msg("gemv_q: unsupported weight type");
 }
 
@@ -961,24 +914,8 @@ int cdna4_launch_gemv_q_fused_ids(const cdna4_gemv_args &a, const float *x, int6
     if (!a.ids || !cdna4_gemv_fused_supported(a.type, a.K, 1) || a.ncol > 65535) return cdna4_set_error_msg("gemv_q_fused_ids: unsupported shape");
     if (((uintptr_t)x | (uintptr_t)(x_row_stride * 4)) & 15) return cdna4_set_error_msg("gemv_q_fused_ids: x rows must be 16-byte aligned");
     if (((uintptr_t)a.W | (uintptr_t)a.w_row_bytes | (uintptr_t)a.w_expert_bytes) & 1) return cdna4_set_error_msg("gemv_q: misaligned operands");
-    switch (a.type) {
-        case CDNA4_Q4_K: case CDNA4_Q5_K:
-            if (((uintptr_t)a.W | (uintptr_t)a.w_row_bytes | (uintptr_t)a.w_expert_bytes) & 15) return cdna4_set_error_msg("gemv_q: Q4_K/Q5_K rows must be 16-byte aligned");
-            if (a.K % 256) return cdna4_set_error_msg("gemv_q: K must be a multiple of 256");
-            return a.type == CDNA4_Q4_K ? launch_fused_ids<CDNA4_Q4_K>(a, x, x_row_stride, st) : launch_fused_ids<CDNA4_Q5_K>(a, x, x_row_stride, st);
-        case CDNA4_Q6_K:
-            if (a.K % 256) return cdna4_set_error_msg("gemv_q: K must be a multiple of 256");
-            return launch_fused_ids<CDNA4_Q6_K>(a, x, x_row_stride, st);
-        case CDNA4_Q4_0: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_fused_ids<CDNA4_Q4_0>(a, x, x_row_stride, st);
-        case CDNA4_Q8_0: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_fused_ids<CDNA4_Q8_0>(a, x, x_row_stride, st);
-        case CDNA4_Q5_0: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_fused_ids<CDNA4_Q5_0>(a, x, x_row_stride, st);
-        case CDNA4_Q4_1: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_fused_ids<CDNA4_Q4_1>(a, x, x_row_stride, st);
-        case CDNA4_Q5_1: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_fused_ids<CDNA4_Q5_1>(a, x, x_row_stride, st);
-        case CDNA4_IQ4_NL: if (a.K % 32) return cdna4_set_error_msg("gemv_q: K must be a multiple of 32"); return launch_fused_ids<CDNA4_IQ4_NL>(a, x, x_row_stride, st);
-        case CDNA4_Q2_K: if (a.K % 256) return cdna4_set_error_msg("gemv_q: K must be a multiple of 256"); return launch_fused_ids<CDNA4_Q2_K>(a, x, x_row_stride, st);
-        case CDNA4_Q3_K: if (a.K % 256) return cdna4_set_error_msg("gemv_q: K must be a multiple of 256"); return launch_fused_ids<CDNA4_Q3_K>(a, x, x_row_stride, st);
-        case CDNA4_IQ4_XS: if (a.K % 256) return cdna4_set_error_msg("gemv_q: K must be a multiple of 256"); return launch_fused_ids<CDNA4_IQ4_XS>(a, x, x_row_stride, st);
-    }
+    int rc = gemv_operands_ok(a.type, a.K, a.W, a.w_row_bytes, a.w_expert_bytes);
+    if (rc || cdna4_dispatch(cdna4_all12{}, a.type, [&](auto t) { rc = launch_fused_ids<t.value>(a, x, x_row_stride, st); })) return rc;
     return cdna4_set_error_msg("gemv_q: unsupported weight type");
 }
 
@@ -1002,12 +939,7 @@ int cdna4_launch_gemv_q_fused_grp(int type, const cdna4_gemv_group &g, int n, co
         if (g.M[i] <= 0 || !g.W[i] || !g.Y[i]) return cdna4_set_error_msg("gemv_q_fused_grp: bad matrix");
         if (((uintptr_t)g.W[i] | (uintptr_t)g.w_row_bytes[i]) & ((type == CDNA4_Q4_K || type == CDNA4_Q5_K) ? 15 : 1)) return cdna4_set_error_msg("gemv_q_fused_grp: misaligned weight rows");
     }
-    switch (type) {
-        case CDNA4_Q4_K: return launch_fused_grp<CDNA4_Q4_K>(g, n, x, st);
-        case CDNA4_Q5_K: return launch_fused_grp<CDNA4_Q5_K>(g, n, x, st);
-        case CDNA4_Q6_K: return launch_fused_grp<CDNA4_Q6_K>(g, n, x, st);
-        case CDNA4_Q4_0: return launch_fused_grp<CDNA4_Q4_0>(g, n, x, st);
-        case CDNA4_Q8_0: return launch_fused_grp<CDNA4_Q8_0>(g, n, x, st);
-    }
+    int rc = gemv_operands_ok(type, g.K, g.W[0], g.w_row_bytes[0]);           // (the rows: checked above, matrix by matrix; here for K)
+    if (rc || cdna4_dispatch(cdna4_main5{}, type, [&](auto t) { rc = launch_fused_grp<t.value>(g, n, x, st); })) return rc;
     return cdna4_set_error_msg("gemv_q_fused_grp: the five headline formats");
 }

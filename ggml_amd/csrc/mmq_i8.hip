@@ -22,6 +22,7 @@
 //   * per superblock and lane: sumi[i] = sum_j sc_j S_j[i] and summs[i] = sum_j m_j bs_j[i] in int32 (v_mad_i32_i24), then
 //     acc[i] += (d dy_i) sumi[i] - (dmin dy_i) summs[i] in fp32 — the association of ggml_vec_dot_q4_K_q8_K's scalar body.
 #include "cdna4_common.h"
+#include "cdna4_formats.hpp"
 #include "cdna4_kernels.h"
 #include "epilogue.h"
 
@@ -485,7 +486,7 @@ __global__ __launch_bounds__(NW * 64) void k_mmq_q6_K(mmq_args a) {
 //  the last one's sum, with nothing to overlap it.  Removed.)
 bool cdna4_mmq_supported(int type, int64_t M, int64_t K, int64_t B) {
     if (type == CDNA4_Q6_K && B > 32) return false;                   // (its three- and four-group forms spill: two accumulator sets per block pair)
-    return (type == CDNA4_Q4_K || type == CDNA4_Q5_K || type == CDNA4_Q6_K || type == CDNA4_Q4_0 || type == CDNA4_Q8_0) && M > 0 && K >= 256 && K % 256 == 0 && B >= 2 && B <= 64;
+    return cdna4_type_is_main5(type) && M > 0 && K >= 256 && K % 256 == 0 && B >= 2 && B <= 64;
 }
 template <int TYPE>
 static void launch_q80act(const mmq_args &a, int ncg, dim3 grid, hipStream_t st) {
@@ -498,7 +499,7 @@ static void launch_q80act(const mmq_args &a, int ncg, dim3 grid, hipStream_t st)
 // multiple of 128), one launch over (16 weight rows) x (32-row chunks of the image); chunks past an expert's run exit.  For few rows per expert — where the
 // grouped fp16 GEMM multiplies 128-row tiles that are mostly padding — and on the CPU's own integer arithmetic (rel-L2 ~2e-7 instead of 3e-4).
 bool cdna4_mmq_ids_supported(int type, int64_t K) {
-    return (type == CDNA4_Q4_K || type == CDNA4_Q5_K || type == CDNA4_Q6_K || type == CDNA4_Q4_0 || type == CDNA4_Q8_0) && K >= 256 && K % 256 == 0;
+    return cdna4_type_is_main5(type) && K >= 256 && K % 256 == 0;
 }
 int cdna4_launch_mmq_ids(const cdna4_gemv_args &g, const int32_t *tile_expert, const int32_t *row_dst, int64_t w_expert_bytes, hipStream_t st) {
     if (!cdna4_mmq_ids_supported(g.type, g.K) || g.ncol % 128 || !tile_expert || !row_dst) return cdna4_set_error_msg("mmq_ids: unsupported type / shape");

@@ -4,6 +4,7 @@
 // next to each kernel); compiled with -ffp-contract=off so mul-then-add sequences round like the CPU's.
 #include "../../include/ggml_cdna4.h"
 #include "cdna4_common.h"
+#include "cdna4_formats.hpp"
 #include "cdna4_kernels.h"
 #include "epilogue.h"
 #include "quantize_dev.h"
@@ -14,17 +15,10 @@ typedef ggml_cdna4_tensor T4;
 static inline int64_t nelem(const T4 *t) { return t->ne[0] * t->ne[1] * t->ne[2] * t->ne[3]; }
 static inline int64_t nrows(const T4 *t) { return t->ne[1] * t->ne[2] * t->ne[3]; }
 static inline size_t tsize(int type) {
-    switch (type) { case CDNA4_F32: case CDNA4_I32: return 4; case CDNA4_F16: case CDNA4_BF16: return 2; case CDNA4_Q4_0: return 18; case CDNA4_Q8_0: return 34;
-                    case CDNA4_Q4_K: return 144; case CDNA4_Q5_K: return 176; case CDNA4_Q6_K: return 210;
-                    case CDNA4_Q4_1: return 20; case CDNA4_Q5_0: return 22; case CDNA4_Q5_1: return 24; case CDNA4_Q2_K: return 84; case CDNA4_Q3_K: return 110;
-                    case CDNA4_IQ4_NL: return 18; case CDNA4_IQ4_XS: return 136; }
-    return 0;
+    switch (type) { case CDNA4_F32: case CDNA4_I32: return 4; case CDNA4_F16: case CDNA4_BF16: return 2; }
+    return (size_t)cdna4_type_bytes(type);
 }
-static inline int bsize(int type) {
-    switch (type) { case CDNA4_Q4_0: case CDNA4_Q8_0: case CDNA4_Q4_1: case CDNA4_Q5_0: case CDNA4_Q5_1: case CDNA4_IQ4_NL: return 32;
-                    case CDNA4_Q4_K: case CDNA4_Q5_K: case CDNA4_Q6_K: case CDNA4_Q2_K: case CDNA4_Q3_K: case CDNA4_IQ4_XS: return 256; }
-    return 1;
-}
+static inline int bsize(int type) { const int qk = cdna4_type_qk(type); return qk ? qk : 1; }
 static inline bool is_contig(const T4 *t) {      // ggml_is_contiguous
     const int64_t bs = bsize(t->type);
     if (t->nb[0] != (int64_t)tsize(t->type)) return false;

@@ -693,6 +693,75 @@ def test_32_weight_formats_with_k_not_a_multiple_of_64_on_the_cpu(name, t, k):
     assert mod.mul_mat_id(t, 32, k, 4, 2, 2, 1, seed=k + 1, timeout=300) < 1e-5
 
 
+_GEMV_ENTRY_POINTS = r"""
+import ctypes as C, json, sys
+import numpy as np
+sys.path.insert(0, sys.argv[2])
+import refutil as R
+so, t = C.CDLL(sys.argv[1]), int(sys.argv[3])
+i64, vp = C.c_int64, C.c_void_p
+so.cdna4_emul_alloc.restype = vp; so.cdna4_emul_alloc.argtypes = [C.c_size_t]
+so.ggml_cdna4_mul_mat_workspace_size.restype = C.c_size_t; so.ggml_cdna4_mul_mat_workspace_size.argtypes = [C.c_int, i64, i64]
+so.ggml_cdna4_last_error.restype = C.c_char_p
+so.ggml_cdna4_mul_mat.restype = C.c_int
+so.ggml_cdna4_mul_mat.argtypes = [C.c_int, vp, i64, vp, i64, vp, i64, i64, i64, i64, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp]
+def dev(a):                                     # "device" memory of the emulation: a shared mapping the work-group processes write into
+    a = np.ascontiguousarray(a); p = so.cdna4_emul_alloc(max(a.nbytes, 1))
+    v = np.frombuffer((C.c_uint8 * max(a.nbytes, 1)).from_address(p), a.dtype, a.size).reshape(a.shape); v[...] = a
+    return p, v
+def call(m, k, b, path=0, w_pad=0, k_ref=None):
+    # k_ref: the K the operands are made for (a bad call names another K on them); w_pad: extra bytes between weight rows
+    kr = k_ref or k
+    w = R.random_weights(t, m, kr, seed=t + b).view(np.uint8).reshape(m, -1)
+    x = np.random.default_rng(t + b + 1).uniform(-1, 1, (b, kr)).astype(np.float32)
+    wp, _ = dev(np.pad(w, ((0, 0), (0, w_pad)))); xp, _ = dev(x)
+    yp, y = dev(np.full((b, m), -12345.0, np.float32))
+    nws = so.ggml_cdna4_mul_mat_workspace_size(t, kr, b); ws, _ = dev(np.zeros(nws + 256, np.uint8))
+    rc = so.ggml_cdna4_mul_mat(t, wp, w.shape[1] + w_pad, xp, kr, yp, m, m, k, b, ws, nws, path, 0, 0, None)
+    return rc, y.copy(), (so.ggml_cdna4_last_error() or b"").decode(), R.o_mul_mat(t, w, x, m, kr)
+kq, main5 = R.BLCK[t] == 256, t in (R.Q4_K, R.Q5_K, R.Q6_K, R.Q4_0, R.Q8_0)
+good = [("fused", dict(m=24, k=256, b=1))]
+if main5: good += [("fused_n", dict(m=24, k=256, b=3))]
+good += [("plain", dict(m=24, k=256, b=9, path=1) if kq else dict(m=24, k=288, b=9))]
+bad = [("k", dict(m=24, k=288 if kq else 272, k_ref=512, b=bb)) for bb in (1, 3, 9)]
+if t == R.Q4_K: bad += [("pitch", dict(m=24, k=256, b=bb, w_pad=2, path=pp)) for bb, pp in ((1, 0), (3, 0), (9, 1))]
+out = {"good": [], "bad": []}
+for name, kw in good:
+    rc, y, msg, ref = call(**kw)
+    out["good"].append([name, rc, msg if rc else "", bool((y != -12345.0).all()) and R.rel_l2(y, ref)])
+for name, kw in bad:
+    rc, y, msg, _ = call(**kw)
+    out["bad"].append([name, kw["b"], rc, msg, bool((y == -12345.0).all())])
+print(json.dumps(out))
+"""
+
+
+@pytest.mark.parametrize("name,t", LIB_TYPES)
+def test_whole_library_gemv_entry_points_accept_and_reject_on_the_cpu(name, t):
+    """every weight type through ggml_cdna4_mul_mat of the emulated library at the smallest shapes that reach each GEMV launcher of gemv_q.hip — one row (the one-launch
+    form), three rows of the five headline formats (the one-launch form for 2..8 rows), nine rows on the plain quantize + GEMV pair (K = 288 for the 32-weight
+    formats; an explicit GEMV path for the superblock formats) — within the GEMV bar of the oracle.  (The staged form takes over from 32 K activation values per
+    call, beyond these sizes: test_small_batch_decode_kernel_source_on_the_cpu launches it directly.)  And the calls
+    the launchers and the call in front of them refuse: a K that is not a whole number of blocks, and for Q4_K a row pitch that is not a multiple of 16 bytes.
+    Those return non-zero with their own message and leave the output untouched."""
+    import json
+    import sys
+    mod = _emul_module("lib_emul_check")
+    r = subprocess.run([sys.executable, "-c", _GEMV_ENTRY_POINTS, mod.build_so(), os.path.join(ROOT, "tests"), str(t)], capture_output=True, text=True, timeout=600)
+    if r.returncode == 77:
+        pytest.skip("the environment cannot host the emulation")
+    assert r.returncode == 0, (r.stdout + r.stderr)[-800:]
+    got = json.loads(r.stdout.strip().splitlines()[-1])
+    want = ["fused"] + (["fused_n"] if t in (12, 13, 14, 2, 8) else []) + ["plain"]
+    assert [g[0] for g in got["good"]] == want
+    for form, rc, msg, err in got["good"]:
+        assert rc == 0 and err is not False and err < 1e-5, (name, form, rc, msg, err)
+    assert len(got["bad"]) == (6 if t == 12 else 3)
+    for kind, b, rc, msg, untouched in got["bad"]:
+        assert rc != 0 and untouched, (name, kind, b, rc, msg)
+        assert msg == ("mul_mat: K is not a whole number of blocks" if kind == "k" else "gemv_q: Q4_K/Q5_K rows must be 16-byte aligned"), (name, kind, b, msg)
+
+
 @pytest.mark.parametrize("t,m,k,ne,nu,nb,nt", [(12, 128, 512, 4, 2, 2, 32), (12, 64, 256, 8, 2, 1, 40), (12, 130, 768, 3, 2, 2, 70),
                                                 (13, 130, 512, 3, 2, 2, 40), (14, 64, 256, 4, 2, 1, 40), (2, 130, 384, 3, 2, 2, 40), (8, 64, 256, 4, 2, 2, 33)])
 def test_whole_library_grouped_mul_mat_id_on_the_cpu(t, m, k, ne, nu, nb, nt):

@@ -38,7 +38,7 @@ _locked = _blm.locked          # (xdist workers share build/: one build at a tim
 def build():
     os.makedirs(OBJ, exist_ok=True)
     exe = os.path.join(OBJ, "lib_emul")
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))] + [os.path.join(HERE, "lib_emul.h"), os.path.join(HERE, "hip_emul.h"), os.path.join(ROOT, "include", "ggml_cdna4.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc", ".hpp"))] + [os.path.join(HERE, "lib_emul.h"), os.path.join(HERE, "hip_emul.h"), os.path.join(ROOT, "include", "ggml_cdna4.h")]
     newest = max(os.path.getmtime(d) for d in deps)
 
     def one(f):
@@ -63,7 +63,7 @@ def build_so():
     pic = os.path.join(OBJ, "pic")
     os.makedirs(pic, exist_ok=True)
     out = os.path.join(OBJ, "libcdna4_emul.so")
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))] + [os.path.join(HERE, "lib_emul.h"), os.path.join(HERE, "hip_emul.h"), os.path.join(ROOT, "include", "ggml_cdna4.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc", ".hpp"))] + [os.path.join(HERE, "lib_emul.h"), os.path.join(HERE, "hip_emul.h"), os.path.join(ROOT, "include", "ggml_cdna4.h")]
     newest = max(os.path.getmtime(d) for d in deps)
     tus = TUS + ["fattn.hip", "lib_emul_so.cpp"]
 
