@@ -1088,13 +1088,158 @@ extern "C" int ggml_cdna4_op_flash_attn_ext_supported(int64_t head_size, int kv_
     if (head_size <= 0 || head_size > 256) return 0;
     return kv_type == CDNA4_F16 || kv_type == CDNA4_BF16 || (cdna4_to_f16_dense_supported(kv_type) && head_size % 32 == 0);
 }
-
-static int fa_f16(const T4 *q, const T4 *k, const T4 *v, const T4 *mask, const T4 *d, float scale, float max_bias, float logit_softcap, void *stream);
-// prefill that fills the chip takes the 128-row kernels (K / V staged through LDS as fp16), everything else the key-split kernel
-// (CDNA4_FA_WIDE_MIN: measurement knob — the smallest number of 128-row work-groups that takes them; default: one per CU)
-static bool fa_takes_wide(int64_t N, int64_t H, int64_t B3) {
+// ---- The launch plan: everything a call does after its argument checks — staging, kernel family and form, key split, merge, grids, LDS and scratch sizes.  fa_make_plan fills it from
+// the descriptors alone: it reads its arguments, cdna4_gemm_cu_count() and the CDNA4_FA_* knobs, and allocates, launches and reports nothing; ggml_cdna4_op_flash_attn_ext executes it.
+enum { FA_STAGE_NONE, FA_STAGE_COPY, FA_STAGE_PAD };                     // K / V read as they are | fp16 copy of the K / V that are not F16 | zero-padded copies of q, K, V and dst
+enum { FA_PIPE, FA_WIDE, FA_SPLIT };                                     // k_flash_attn_pipe | k_flash_attn_wide64 / _wide | k_flash_attn_split
+enum { FA_MERGE_NONE, FA_MERGE_TILES, FA_MERGE_ROWS, FA_MERGE_PIPE };    // - | k_flash_attn_merge | k_flash_attn_merge_rows | k_flash_attn_pipe_merge
+struct fa_plan {
+    int stage, family, kv_type, hs;                                      // kv_type, hs: the K / V type and head size the kernels see (behind the staging)
+    int nw, mode, xcd_map; int64_t qtiles, items;                        // k_flash_attn_pipe: waves per work-group (32 query rows each), mode, XCD map, query tiles, work-groups
+    int nsplit, chunks_per_split, chunk;                                 // key split over work-groups, in chunks of `chunk` keys; nsplit == 1: no kernel reads chunks_per_split (it covers all keys)
+    int pack, mask_vec, merge, block, lds;                               // pack: k_flash_attn_split only (0 otherwise)
+    dim3 grid, fgrid, mgrid; size_t part_bytes, flag_bytes;              // main / k_fa_mask_flags / merge grids; scratch of the partial results (nsplit > 1) and of the chunk flags (0: no flag pass)
+};
+// f(HS, NW, MODE) as integral constants for the forms of k_flash_attn_pipe that exist; false (f not called): there is none.  Only those are instantiated
+// (head size 128 has no 2-wave form: its DMA pieces would straddle the K swizzle's period)
+template <typename F> static inline bool fa_pipe_dispatch(int hs, int nw, int mode, F &&f) {
+    bool hit = false;
+    cdna4_dispatch(cdna4_types<64, 128>{}, hs, [&](auto HS) { cdna4_dispatch(cdna4_types<2, 4, 8>{}, nw, [&](auto NW) {
+        if constexpr (HS.value == 64 || NW.value != 2) hit = cdna4_dispatch(cdna4_types<0, 1, 2>{}, mode, [&](auto MODE) { f(HS, NW, MODE); }); }); });
+    return hit;
+}
+static bool fa_one_grid(int64_t wgs) { return wgs < (1ll << 31); }
+static void fa_split_keys(fa_plan &pl, int64_t nc, int64_t want) { pl.chunks_per_split = (int)((nc + want - 1) / want); pl.nsplit = (int)((nc + pl.chunks_per_split - 1) / pl.chunks_per_split); }
+// the descriptor of a staged copy of t: dense rows of n0 elements of `type` (F16 for K / V, F32 for q / dst); its address comes with the staging
+static T4 fa_dense(T4 t, int type, int64_t n0) { t.data = nullptr; t.type = type; t.ne[0] = n0; t.nb[0] = type == CDNA4_F32 ? 4 : 2; for (int i = 1; i < 4; i++) t.nb[i] = t.nb[i - 1] * t.ne[i - 1]; return t; }
+// the kernels of a call on the K / V they see (behind the staging) at the kernel head size D (q's, padded); exp2: no softcap and a positive scale (what the pipelined kernel's modes 0 / 1 need)
+static fa_plan fa_plan_kernels(const T4 *q, const T4 *k, const T4 *v, const T4 *mask, bool exp2, int64_t D) {
+    const auto n = [](int64_t x) { return std::max<int64_t>(x, 1); };      // (sizes the checks reject, or that leave nothing to do: the plan is total, nothing runs on it)
+    const int64_t N = n(q->ne[1]), H = n(q->ne[2]), B3 = n(q->ne[3]), KV = n(k->ne[1]), rk2 = H / n(k->ne[2]), cus = cdna4_gemm_cu_count();
+    const int kvt = k->type; fa_plan pl{}; pl.kv_type = kvt; pl.hs = (int)D; pl.block = 256; pl.nsplit = 1; pl.chunk = 32; pl.chunks_per_split = (int)((KV + 31) / 32);
+    pl.mask_vec = mask && !(((uintptr_t)mask->data | (uintptr_t)mask->nb[1]) & 15);
+    // head sizes 64 / 128 with an F16 K / V: the pipelined kernel on the largest query tile (256 / 128 / 64 rows) that still gives every CU a work-group
+    // (CDNA4_FA_PIPE: measurement / test knob — 0 keeps the older kernels, 2 / 4 / 8 forces that many waves per work-group whatever the grid)
+    // (beyond its 32-bit source offsets, its chunk list or one grid the call takes the older kernels below: never an error)
+    const bool pipe_fits = KV <= 4095 * 64 && k->nb[1] < (1ll << 25) && v->nb[1] < (1ll << 25) && (!mask || (N + 16) * (int64_t)mask->nb[1] < (1ll << 32)) && fa_one_grid(((N + 63) / 64) * H * B3);
+    if (kvt == CDNA4_F16 && (D == 64 || D == 128) && N > 32 && pipe_fits) {
+        const char *e = getenv("CDNA4_FA_PIPE"), *es = getenv("CDNA4_FA_PIPE_SPLIT");
+        const int64_t nc = (KV + 63) / 64;
+        int nw = e ? atoi(e) : -1;
+        int64_t split = 0;                                             // splits asked for (0: none considered); applied below only where a pipelined form is taken, so no other kernel's plan carries it
+        if (nw < 0) {
+            nw = 0;
+            for (int w = 8; w >= (D == 128 ? 4 : 2) && !nw; w >>= 1)
+                if (((N + 32 * w - 1) / (32 * w)) * H * B3 >= cus) nw = w;
+            // below one work-group per CU: the smallest tile (128 rows at head size 128, 64 at 64) with the keys split over as many work-groups as fill the chip, each split at
+            // least four chunks (CDNA4_FA_PIPE_SPLIT=0: off — then half a chip of 128-row tiles over a short key range, which still beat the key-split kernel: 25.8 against 28.8 us
+            // at 512 x 512 x 32 heads)
+            if (!nw && N >= 128 && !(es && atoi(es) == 0)) {
+                const int w = D == 128 ? 4 : 2;
+                const int64_t it = ((N + 32 * w - 1) / (32 * w)) * H * B3;
+                int64_t want = (cus + it / 2) / it;
+                static const int64_t split_min = getenv("CDNA4_FA_PIPE_SPLIT_MIN") ? atoll(getenv("CDNA4_FA_PIPE_SPLIT_MIN")) : 32;      // (A/B and test knob)
+                if (want > nc / split_min) want = nc / split_min;              // (a split pays from about 32 chunks on: its partial results are written and merged — 512 x 4096 x 32 heads 150 -> 89 us with two splits of 32 chunks, 256 x 2048 46 -> 69 us with four of 8)
+                if (want >= 2) { nw = w; split = want; }
+            }
+            if (!nw && D == 128 && KV <= 1024 && ((N + 127) / 128) * H * B3 >= cus / 2) nw = 4;
+        }
+        if (e && es && atoi(es) > 1) split = std::min<int64_t>(atoi(es), nc);      // (tests: a forced tile height with a forced key split)
+        const int mode = (!exp2 || (mask && !pl.mask_vec)) ? 2 : (mask ? 1 : 0);
+        if (fa_pipe_dispatch((int)D, nw, mode, [&](auto HS, auto NW, auto MODE) { pl.lds = k_flash_attn_pipe_lds<HS.value, NW.value, MODE.value>(); })) {
+            pl.family = FA_PIPE; pl.nw = nw; pl.mode = mode; pl.block = 64 * nw; pl.chunk = 64;
+            if (split) fa_split_keys(pl, nc, split);
+            pl.qtiles = (N + 32 * nw - 1) / (32 * nw); pl.items = pl.qtiles * H * B3 * pl.nsplit; pl.grid = dim3((unsigned)pl.items);
+            if (pl.nsplit > 1) { pl.part_bytes = (size_t)(B3 * H * N) * pl.nsplit * (D + 4) * 4 + 256; pl.merge = FA_MERGE_PIPE; pl.mgrid = dim3((unsigned)((N + 31) / 32), (unsigned)H, (unsigned)B3); }
+            // chunks that are -inf throughout for a whole query tile are not walked (k_fa_mask_flags; bit-neutral): worth a pass over the mask from 2^20 entries on
+            // (CDNA4_FA_NO_SKIP / CDNA4_FA_SKIP_MIN: A/B and test knobs)
+            const int64_t skip_min = getenv("CDNA4_FA_SKIP_MIN") ? atoll(getenv("CDNA4_FA_SKIP_MIN")) : (1ll << 20);      // (tests: 0 takes the pass at any size)
+            if (pl.mask_vec && N * KV >= skip_min && !getenv("CDNA4_FA_NO_SKIP")) { pl.flag_bytes = (size_t)(pl.qtiles * nc) + 256; pl.fgrid = dim3((unsigned)nc, (unsigned)pl.qtiles); }
+            pl.xcd_map = getenv("CDNA4_FA_MAP") ? atoi(getenv("CDNA4_FA_MAP")) : (mask ? 1 : 0);     // (A/B knob; see the kernel)
+            return pl;
+        }
+    }
+    // prefill that fills the chip takes the 128-row kernels (128 query rows per work-group, K / V staged through LDS as fp16), everything else the key-split kernel
+    // (CDNA4_FA_WIDE_MIN: measurement knob — the smallest number of 128-row work-groups that takes them; default: one per CU)
     static const int64_t min_wgs = getenv("CDNA4_FA_WIDE_MIN") ? atoll(getenv("CDNA4_FA_WIDE_MIN")) : 0;
-    return N > 32 && ((N + 127) / 128) * H * B3 >= (min_wgs > 0 ? min_wgs : (int64_t)cdna4_gemm_cu_count());
+    if (N > 32 && ((N + 127) / 128) * H * B3 >= (min_wgs > 0 ? min_wgs : cus)) { pl.family = FA_WIDE; pl.grid = dim3((unsigned)((N + 127) / 128), (unsigned)H, (unsigned)B3); return pl; }
+    // decode / small batches: 32-row query tiles, the keys split over work-groups until the chip is full (one or two work-groups per CU, below), each split
+    // >= 16 chunks
+    // grouped-query decode: the heads of a K / V head in one tile (k_flash_attn_split; CDNA4_FA_NO_PACK: A/B knob)
+    pl.family = FA_SPLIT; pl.pack = (rk2 > 1 && N * rk2 <= 32 && !getenv("CDNA4_FA_NO_PACK")) ? (int)rk2 : 1;
+    const int64_t HT = pl.pack > 1 ? H / pl.pack : H;                // tiles along the head axis
+    const int64_t nchunk = (KV + 31) / 32, qtiles = (N + 31) / 32, tiles = qtiles * HT * B3;
+    // work-groups per CU the split aims at: ONE for F16 / BF16 rows (32 K keys x 32 heads 105.6 -> 99.2 us, grouped-query 8 K / V heads 60.6 -> 43.1: fewer partial results to
+    // write, merge and wait for), TWO for quantized rows, whose conversion is VALU work a second resident work-group hides (Q8_0 88.6 against 108.8, Q4_0 66.7 against 81.4)
+    static const int64_t wgs_knob = getenv("CDNA4_FA_SPLIT_WGS") ? atoll(getenv("CDNA4_FA_SPLIT_WGS")) : 0;      // (A/B knob)
+    const int64_t wgs_per_cu = wgs_knob > 0 ? wgs_knob : (kvt == CDNA4_Q8_0 || kvt == CDNA4_Q4_0 ? 2 : 1);
+    int64_t want = (wgs_per_cu * cus + tiles - 1) / tiles;
+    { static const int64_t min_chunks = getenv("CDNA4_FA_SPLIT_MIN") ? atoll(getenv("CDNA4_FA_SPLIT_MIN")) : 16; if (want > nchunk / min_chunks) want = nchunk / min_chunks; }      // (each split at least 16 chunks — four per wave, which the one-chunk-ahead requests need to pay: 4 K keys x 32 heads 26.4 us at 8, 21.3 at 16, 25.4 at 32; CDNA4_FA_SPLIT_MIN: A/B knob)
+    fa_split_keys(pl, nchunk, want < 1 ? 1 : want);
+    pl.grid = dim3((unsigned)(qtiles * pl.nsplit), (unsigned)HT, (unsigned)B3);
+    if (pl.nsplit > 1) {
+        pl.part_bytes = (size_t)(qtiles * H * B3) * pl.nsplit * 32 * (D + 4) * 4 + 256;      // (per HEAD, also when the heads of a group share a tile)
+        const bool rows = N <= 4 && pl.nsplit <= 512 && !getenv("CDNA4_FA_MERGE_OLD");      // a handful of rows: one work-group per row (CDNA4_FA_MERGE_OLD: A/B knob)
+        pl.merge = rows ? FA_MERGE_ROWS : FA_MERGE_TILES; pl.mgrid = dim3((unsigned)(rows ? N : qtiles), (unsigned)H, (unsigned)B3);
+    }
+    return pl;
+}
+static fa_plan fa_make_plan(const T4 *q, const T4 *k, const T4 *v, const T4 *mask, bool exp2) {
+    const int64_t D = q->ne[0], Dp = D <= 64 ? 64 : (D <= 128 ? 128 : 256); const bool pad = !fa_kernel_head_size(D);
+    // a Q8_0 / Q4_0 / BF16 cache under the key-split kernel (decode, small batches): converted from the raw fragment bytes, no fp16 copy (fa_kv_load / fa_kv_cvt).  Only that kernel
+    // reads a raw cache: a plan for the raw type that is any other kernel means the copy, and the kernels chosen for F16
+    if (!pad && k->type == v->type && (k->type == CDNA4_Q8_0 || k->type == CDNA4_Q4_0 || k->type == CDNA4_BF16) && q->ne[1] < 128 && !getenv("CDNA4_FA_KV_COPY") &&      // (from 128 query rows on the F16 kernels' tiles and key split pay for the copy)
+        !(((uintptr_t)k->data | (uintptr_t)v->data | (uintptr_t)k->nb[1] | (uintptr_t)k->nb[2] | (uintptr_t)k->nb[3] | (uintptr_t)v->nb[1] | (uintptr_t)v->nb[2] | (uintptr_t)v->nb[3]) & (k->type == CDNA4_BF16 ? 15 : 3))) {
+        const fa_plan raw = fa_plan_kernels(q, k, v, mask, exp2, Dp);
+        if (raw.family == FA_SPLIT) return raw;
+    }
+    const T4 ks = pad || k->type != CDNA4_F16 ? fa_dense(*k, CDNA4_F16, Dp) : *k, vs = pad || v->type != CDNA4_F16 ? fa_dense(*v, CDNA4_F16, Dp) : *v;
+    fa_plan pl = fa_plan_kernels(q, &ks, &vs, mask, exp2, Dp);
+    pl.stage = pad ? FA_STAGE_PAD : (k->type == CDNA4_F16 && v->type == CDNA4_F16 ? FA_STAGE_NONE : FA_STAGE_COPY);
+    return pl;
+}
+// fills fattn_params and runs the kernel part of a plan: scratch, the optional flag pass, the main launch, the optional merge
+static int fa_run(const fa_plan &pl, const T4 *q, const T4 *k, const T4 *v, const T4 *mask, const T4 *d, float scale, float max_bias, float logit_softcap, hipStream_t st) {
+    const int64_t H = q->ne[2], B3 = q->ne[3];
+    fattn_params p{};
+    p.q = (const char *)q->data; p.k = (const char *)k->data; p.v = (const char *)v->data; p.mask = mask ? (const char *)mask->data : nullptr; p.dst = (float *)d->data;
+    p.q_nb1 = q->nb[1]; p.q_nb2 = q->nb[2]; p.q_nb3 = q->nb[3];
+    p.k_nb1 = k->nb[1]; p.k_nb2 = k->nb[2]; p.k_nb3 = k->nb[3]; p.v_nb1 = v->nb[1]; p.v_nb2 = v->nb[2]; p.v_nb3 = v->nb[3]; p.mask_nb1 = mask ? mask->nb[1] : 0;
+    p.n_q = (int)q->ne[1]; p.n_head = (int)H; p.n_kv = (int)k->ne[1];
+    p.rk2 = (int)(H / k->ne[2]); p.rk3 = (int)(B3 / k->ne[3]); p.rv2 = (int)(H / v->ne[2]); p.rv3 = (int)(B3 / v->ne[3]);
+    // ggml-cpu.c:10876-10884
+    p.scale = logit_softcap != 0.0f ? scale / logit_softcap : scale; p.max_bias = max_bias; p.logit_softcap = logit_softcap;
+    p.n_head_log2 = 1u << (uint32_t)floorf(log2f((float)H));
+    p.m0 = powf(2.0f, -(max_bias) / p.n_head_log2); p.m1 = powf(2.0f, -(max_bias / 2.0f) / p.n_head_log2);
+    p.mask_vec = pl.mask_vec; p.nsplit = pl.nsplit; p.chunks_per_split = pl.chunks_per_split; p.pack = pl.pack;
+    NEED(pl.family == FA_SPLIT || pl.kv_type == CDNA4_F16, "flash_attn_ext: the 128-row kernels take an F16 K / V");
+    NEED(pl.family != FA_PIPE || fa_one_grid(pl.items), "flash_attn_ext: too many query tiles for one grid");      // (a forced key split: pipe_fits counted the tiles alone)
+    if (pl.part_bytes) NEED(p.part = (float *)cdna4_gemm_scratch(pl.part_bytes, 4), "flash_attn_ext: cannot allocate the key-split scratch");
+    uint8_t *flags = nullptr;
+    if (pl.flag_bytes) {
+        NEED(flags = (uint8_t *)cdna4_gemm_scratch(pl.flag_bytes, 11), "flash_attn_ext: cannot allocate the chunk flags");
+        hipLaunchKernelGGL(k_fa_mask_flags, pl.fgrid, dim3(256), 0, st, p, 32 * pl.nw, (int)pl.fgrid.x, flags); CDNA4_CHECK_LAUNCH();
+    }
+    int rc = 0; bool hit = false; const dim3 block((unsigned)pl.block);
+    if (pl.family == FA_PIPE) hit = fa_pipe_dispatch(pl.hs, pl.nw, pl.mode, [&](auto HS, auto NW, auto MODE) {
+        if (pl.lds > 64 * 1024) rc = cdna4_raise_lds_limit<k_flash_attn_pipe<HS.value, NW.value, MODE.value>>(pl.lds, "flash_attn_ext: cannot raise the dynamic LDS limit");
+        if (!rc) hipLaunchKernelGGL((k_flash_attn_pipe<HS.value, NW.value, MODE.value>), pl.grid, block, pl.lds, st, p, (int)pl.qtiles, pl.xcd_map, (const uint8_t *)flags);
+    });
+    else cdna4_dispatch(cdna4_types<64, 128, 256>{}, pl.hs, [&](auto HS) {
+        // (128-row kernels — head sizes 64 / 128: 64-key chunks; 256: the 32-key-chunk kernel — its forms for the smaller heads were an A/B knob of round 3 and went in round 5)
+        if (pl.family == FA_WIDE) { if constexpr (HS.value == 256) hipLaunchKernelGGL(k_flash_attn_wide<256>, pl.grid, block, 0, st, p); else hipLaunchKernelGGL(k_flash_attn_wide64<HS.value>, pl.grid, block, 0, st, p); hit = true; }
+        else hit = cdna4_dispatch(cdna4_types<CDNA4_F16, CDNA4_BF16, CDNA4_Q8_0, CDNA4_Q4_0>{}, pl.kv_type, [&](auto KVT) { hipLaunchKernelGGL((k_flash_attn_split<HS.value, KVT.value>), pl.grid, block, 0, st, p); });
+    });
+    if (rc) return rc;
+    NEED(hit, "flash_attn_ext: no kernel of this head size for this K / V type");      // (the checks leave none such: a plan that names no kernel must not pass for a result)
+    CDNA4_CHECK_LAUNCH();
+    if (pl.merge != FA_MERGE_NONE) cdna4_dispatch(cdna4_types<64, 128, 256>{}, pl.hs, [&](auto HS) {
+        if (pl.merge == FA_MERGE_TILES) hipLaunchKernelGGL(k_flash_attn_merge<HS.value>, pl.mgrid, dim3(256), 0, st, p);
+        else if (pl.merge == FA_MERGE_ROWS) hipLaunchKernelGGL(k_flash_attn_merge_rows<HS.value>, pl.mgrid, dim3(256), 0, st, p);
+        else if constexpr (HS.value != 256) hipLaunchKernelGGL(k_flash_attn_pipe_merge<HS.value>, pl.mgrid, dim3(256), 0, st, p);
+    });
+    CDNA4_CHECK_LAUNCH();
+    return 0;
 }
 
 // A BF16 K / V takes the same route (bf16 -> fp16: exact for |x| in [2^-14, 65504], the range a KV cache lives in; the CPU rounds q to bf16 instead,
@@ -1103,69 +1248,39 @@ static bool fa_takes_wide(int64_t N, int64_t H, int64_t B3) {
 // fp16, dense [batch][head][n_kv][head_size] in library scratch: one pass over the cache), then the F16 kernels run on the copy.  The CPU
 // instead quantizes q to the K type's vec_dot_type and takes integer dots (ggml-cpu.c:10921-10960); both are approximations of the same
 // product, ours keeps q in fp16 like ggml-cuda's kernels do — inside the stock harness's gate, and closer to a float64 evaluation.
-extern "C" int ggml_cdna4_op_flash_attn_ext(const T4 *q, const T4 *k, const T4 *v, const T4 *mask, const T4 *d,
+extern "C" int ggml_cdna4_op_flash_attn_ext(const T4 *q_in, const T4 *k_in, const T4 *v_in, const T4 *mask, const T4 *d_in,
                                             float scale, float max_bias, float logit_softcap, void *stream) {
-    NEED(q && k && v && d, "flash_attn_ext: q, k, v and dst are required");
+    NEED(q_in && k_in && v_in && d_in, "flash_attn_ext: q, k, v and dst are required");
     // Head sizes without a kernel of their own (80, 96, 112, ...) run ZERO-PADDED to the next of 64 / 128 / 256: the padded components of q and k
     // add 0 to every score, the padded columns of v produce output columns that are dropped.  q, k, v are copied into padded scratch (k / v as
     // fp16), the result is computed into padded scratch and its first head_size columns copied out — four extra passes, all plain strided copies.
-    const int64_t D = q->ne[0], Dp = D <= 64 ? 64 : (D <= 128 ? 128 : 256);
+    const int64_t D = q_in->ne[0], N = q_in->ne[1], H = q_in->ne[2], B3 = q_in->ne[3];
     NEED(D > 0 && D <= 256, "flash_attn_ext: head size must be 1..256");
-    const bool pad = !fa_kernel_head_size(D);
-    if (!pad && k->type == CDNA4_F16 && v->type == CDNA4_F16) return fa_f16(q, k, v, mask, d, scale, max_bias, logit_softcap, stream);
-    // a Q8_0 / Q4_0 / BF16 cache under the key-split kernel (decode, small batches): converted from the raw fragment bytes, no fp16 copy (fa_kv_load / fa_kv_cvt)
-    if (!pad && k->type == v->type && (k->type == CDNA4_Q8_0 || k->type == CDNA4_Q4_0 || k->type == CDNA4_BF16) && q->ne[1] > 0 && q->ne[2] > 0 && q->ne[3] > 0 &&
-        !fa_takes_wide(q->ne[1], q->ne[2], q->ne[3]) && q->ne[1] < 128 && !getenv("CDNA4_FA_KV_COPY") &&      // (from 128 query rows on the F16 kernels' tiles and key split pay for the copy)
-        !(((uintptr_t)k->data | (uintptr_t)v->data | (uintptr_t)k->nb[1] | (uintptr_t)k->nb[2] | (uintptr_t)k->nb[3] | (uintptr_t)v->nb[1] | (uintptr_t)v->nb[2] | (uintptr_t)v->nb[3]) & (k->type == CDNA4_BF16 ? 15 : 3)))
-        return fa_f16(q, k, v, mask, d, scale, max_bias, logit_softcap, stream);
-    hipStream_t st = (hipStream_t)stream;
-    T4 kv[2] = {*k, *v}, qq = *q, dd = *d;
+    const fa_plan pl = fa_make_plan(q_in, k_in, v_in, mask, logit_softcap == 0.0f && scale > 0.0f);      // (no side effects; the checks below ask what its staging asks)
+    const bool pad = pl.stage == FA_STAGE_PAD; const int64_t Dp = pl.hs;      // (pl.hs: q's head size, padded — what k, v and dst are held to below)
+    // the checks, on the descriptors the kernels will see: a staged tensor's is that of its copy, whose address comes with the staging below
+    T4 kv[2] = {*k_in, *v_in}, qq = *q_in, dd = *d_in;
+    const T4 *q = &qq, *k = &kv[0], *v = &kv[1], *d = &dd;
+    bool staged[2];
     for (int i = 0; i < 2; i++) {
         T4 &t = kv[i];
-        if (t.type == CDNA4_F16 && !pad) continue;
+        if (!(staged[i] = pl.stage != FA_STAGE_NONE && (t.type != CDNA4_F16 || pad))) continue;
         NEED(t.type == CDNA4_F16 || cdna4_to_f16_dense_supported(t.type), "flash_attn_ext: k / v must be F16, BF16 or Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0");
         NEED(t.ne[0] == D && (t.type == CDNA4_F16 || t.type == CDNA4_BF16 || D % 32 == 0) && t.ne[1] > 0 && t.ne[2] > 0 && t.ne[3] > 0, "flash_attn_ext: bad k / v shape");
-        const size_t bytes = (size_t)(Dp * t.ne[1] * t.ne[2] * t.ne[3]) * 2;
-        void *dense = cdna4_gemm_scratch(bytes + 256, 5 + i);
-        NEED(dense, "flash_attn_ext: cannot allocate the fp16 copy of k / v");
-        if (pad && hipMemsetAsync(dense, 0, bytes, st) != hipSuccess) { (void)hipGetLastError(); return cdna4_set_error_msg("flash_attn_ext: memset failed"); }
-        T4 c = t;                                                      // the copy: head_size columns of rows Dp halves apart
-        c.data = dense; c.type = CDNA4_F16; c.nb[0] = 2; c.nb[1] = 2 * Dp; c.nb[2] = c.nb[1] * c.ne[1]; c.nb[3] = c.nb[2] * c.ne[2];
-        const int rc = t.type == CDNA4_F16 ? ggml_cdna4_op_cpy(&t, &c, 0, stream) : cdna4_launch_to_f16_dense(&t, dense, Dp, st);
-        if (rc) return rc;
-        t = c; t.ne[0] = Dp;
+        t = fa_dense(t, CDNA4_F16, Dp);
     }
     if (pad) {
-        const int64_t N = q->ne[1], H = q->ne[2], B3 = q->ne[3];
         NEED(q->type == CDNA4_F32 && d->type == CDNA4_F32 && N > 0 && H > 0 && B3 > 0, "flash_attn_ext: F32 q / dst");
         NEED(d->ne[0] == D && d->ne[1] == H && d->ne[2] == N && d->ne[3] == B3, "flash_attn_ext: dst must be [head_size, n_head, n_q, batch]");
-        const size_t nel = (size_t)(Dp * N * H * B3);
-        float *qp = (float *)cdna4_gemm_scratch(nel * 4 + 256, 7), *dp = (float *)cdna4_gemm_scratch(nel * 4 + 256, 8);
-        NEED(qp && dp, "flash_attn_ext: cannot allocate the padded q / dst");
-        if (hipMemsetAsync(qp, 0, nel * 4, st) != hipSuccess) { (void)hipGetLastError(); return cdna4_set_error_msg("flash_attn_ext: memset failed"); }
-        T4 c = *q; c.data = qp; c.nb[0] = 4; c.nb[1] = 4 * Dp; c.nb[2] = c.nb[1] * N; c.nb[3] = c.nb[2] * H;
-        int rc = ggml_cdna4_op_cpy(q, &c, 0, stream);
-        if (rc) return rc;
-        qq = c; qq.ne[0] = Dp;
-        dd = *d; dd.data = dp; dd.ne[0] = Dp; dd.nb[0] = 4; dd.nb[1] = 4 * Dp; dd.nb[2] = dd.nb[1] * H; dd.nb[3] = dd.nb[2] * N;
-        rc = fa_f16(&qq, &kv[0], &kv[1], mask, &dd, scale, max_bias, logit_softcap, stream);
-        if (rc) return rc;
-        T4 view = dd; view.ne[0] = D;                                  // the first head_size columns of every padded output row
-        return ggml_cdna4_op_cpy(&view, d, 0, stream);
+        qq = fa_dense(qq, CDNA4_F32, Dp); dd = fa_dense(dd, CDNA4_F32, Dp);
     }
-    return fa_f16(q, &kv[0], &kv[1], mask, d, scale, max_bias, logit_softcap, stream);
-}
-
-static int fa_f16(const T4 *q, const T4 *k, const T4 *v, const T4 *mask, const T4 *d, float scale, float max_bias, float logit_softcap, void *stream) {
-    const int kvt = k->type;                                      // F16, or Q8_0 / Q4_0 (key-split kernel only: ggml_cdna4_op_flash_attn_ext decides)
-    const bool kvq = kvt == CDNA4_Q8_0 || kvt == CDNA4_Q4_0;
+    const int kvt = k->type;                                      // F16, or the raw BF16 / Q8_0 / Q4_0 of the key-split kernel
+    const bool kvq = kvt == CDNA4_Q8_0 || kvt == CDNA4_Q4_0; const int64_t KV = k->ne[1];
     NEED(q->type == CDNA4_F32 && d->type == CDNA4_F32 && v->type == kvt && (kvt == CDNA4_F16 || kvt == CDNA4_BF16 || kvq), "flash_attn_ext: F32 q / dst and F16 k / v only");
-    const int64_t D = q->ne[0], N = q->ne[1], H = q->ne[2], B3 = q->ne[3], KV = k->ne[1];
-    NEED(fa_kernel_head_size(D), "flash_attn_ext: head size must be 64, 128 or 256");
-    NEED(k->ne[0] == D && v->ne[0] == D && v->ne[1] == KV && k->ne[2] == v->ne[2] && k->ne[3] == v->ne[3], "flash_attn_ext: k / v shape mismatch");
+    NEED(k->ne[0] == Dp && v->ne[0] == Dp && v->ne[1] == KV && k->ne[2] == v->ne[2] && k->ne[3] == v->ne[3], "flash_attn_ext: k / v shape mismatch");
     NEED(k->ne[2] > 0 && k->ne[3] > 0 && H % k->ne[2] == 0 && B3 % k->ne[3] == 0, "flash_attn_ext: heads / batch not broadcastable over k / v");
-    NEED(d->ne[0] == D && d->ne[1] == H && d->ne[2] == N && d->ne[3] == B3, "flash_attn_ext: dst must be [head_size, n_head, n_q, batch]");
-    NEED(d->nb[0] == 4 && d->nb[1] == 4 * D && d->nb[2] == d->nb[1] * H && d->nb[3] == d->nb[2] * N, "flash_attn_ext: dst must be contiguous");
+    NEED(d->ne[0] == Dp && d->ne[1] == H && d->ne[2] == N && d->ne[3] == B3, "flash_attn_ext: dst must be [head_size, n_head, n_q, batch]");
+    NEED(d->nb[0] == 4 && d->nb[1] == 4 * Dp && d->nb[2] == d->nb[1] * H && d->nb[3] == d->nb[2] * N, "flash_attn_ext: dst must be contiguous");
     NEED(q->nb[0] == 4 && (kvq || (k->nb[0] == 2 && v->nb[0] == 2)), "flash_attn_ext: rows must be contiguous");
     NEED(!(((uintptr_t)k->data | (uintptr_t)v->data | (uintptr_t)d->data | (uintptr_t)k->nb[1] | (uintptr_t)k->nb[2] | (uintptr_t)k->nb[3] |
             (uintptr_t)v->nb[1] | (uintptr_t)v->nb[2] | (uintptr_t)v->nb[3]) & (kvq ? 3 : 15)) && !((uintptr_t)d->data & 15), "flash_attn_ext: k / v rows and dst must be 16-byte aligned");
@@ -1173,143 +1288,28 @@ static int fa_f16(const T4 *q, const T4 *k, const T4 *v, const T4 *mask, const T
     if (mask) {
         NEED(mask->type == CDNA4_F16 && mask->nb[0] == 2 && mask->ne[0] == KV && mask->ne[1] >= N && mask->ne[2] == 1 && mask->ne[3] == 1, "flash_attn_ext: mask must be F16 [n_kv, >= n_q]");
     } else NEED(max_bias == 0.0f, "flash_attn_ext: ALiBi needs a mask");
-    if (N <= 0 || H <= 0 || B3 <= 0 || D <= 0) return 0;
+    if (N <= 0 || H <= 0 || B3 <= 0) return 0;
     NEED(KV > 0, "flash_attn_ext: no keys");
     NEED(H <= 65535 && B3 <= 65535, "flash_attn_ext: too many heads / batches for one grid");
-
-    fattn_params p{};
-    p.q = (const char *)q->data; p.k = (const char *)k->data; p.v = (const char *)v->data; p.mask = mask ? (const char *)mask->data : nullptr; p.dst = (float *)d->data;
-    p.q_nb1 = q->nb[1]; p.q_nb2 = q->nb[2]; p.q_nb3 = q->nb[3];
-    p.k_nb1 = k->nb[1]; p.k_nb2 = k->nb[2]; p.k_nb3 = k->nb[3]; p.v_nb1 = v->nb[1]; p.v_nb2 = v->nb[2]; p.v_nb3 = v->nb[3];
-    p.mask_nb1 = mask ? mask->nb[1] : 0;
-    p.n_q = (int)N; p.n_head = (int)H; p.n_kv = (int)KV;
-    p.rk2 = (int)(H / k->ne[2]); p.rk3 = (int)(B3 / k->ne[3]); p.rv2 = (int)(H / v->ne[2]); p.rv3 = (int)(B3 / v->ne[3]);
-    // ggml-cpu.c:10876-10884
-    p.scale = logit_softcap != 0.0f ? scale / logit_softcap : scale; p.max_bias = max_bias; p.logit_softcap = logit_softcap;
-    p.n_head_log2 = 1u << (uint32_t)floorf(log2f((float)H));
-    p.m0 = powf(2.0f, -(max_bias) / p.n_head_log2); p.m1 = powf(2.0f, -(max_bias / 2.0f) / p.n_head_log2);
-    p.nsplit = 1; p.chunks_per_split = (int)((KV + 31) / 32); p.part = nullptr;
     hipStream_t st = (hipStream_t)stream;
-
-    p.mask_vec = mask && !(((uintptr_t)mask->data | (uintptr_t)mask->nb[1]) & 15);
-    const int64_t cus = cdna4_gemm_cu_count();
-    // head sizes 64 / 128 with an F16 K / V: the pipelined kernel on the largest query tile (256 / 128 / 64 rows) that still gives every CU a work-group
-    // (CDNA4_FA_PIPE: measurement / test knob — 0 keeps the older kernels, 2 / 4 / 8 forces that many waves per work-group whatever the grid)
-    // (beyond its 32-bit source offsets, its chunk list or one grid the call takes the older kernels below)
-    const bool pipe_fits = KV <= 4095 * 64 && k->nb[1] < (1ll << 25) && v->nb[1] < (1ll << 25) && (!mask || (N + 16) * (int64_t)mask->nb[1] < (1ll << 32)) && ((N + 63) / 64) * H * B3 < (1ll << 31);
-    if (kvt == CDNA4_F16 && (D == 64 || D == 128) && N > 32 && pipe_fits) {
-        const char *e = getenv("CDNA4_FA_PIPE");
-        int nw = e ? atoi(e) : -1;
-        if (nw < 0) {
-            nw = 0;
-            for (int c = 8; c >= (D == 128 ? 4 : 2) && !nw; c >>= 1)          // (head size 128 has no 2-wave form: its DMA pieces would straddle the K swizzle's period)
-                if (((N + 32 * c - 1) / (32 * c)) * H * B3 >= cus) nw = c;
-            // below one work-group per CU: the smallest tile (128 rows at head size 128, 64 at 64) with the keys split over as many work-groups as fill the chip, each split at
-            // least four chunks (CDNA4_FA_PIPE_SPLIT=0: off — then half a chip of 128-row tiles over a short key range, which still beat the key-split kernel: 25.8 against 28.8 us
-            // at 512 x 512 x 32 heads)
-            if (!nw && N >= 128 && !(getenv("CDNA4_FA_PIPE_SPLIT") && atoi(getenv("CDNA4_FA_PIPE_SPLIT")) == 0)) {
-                const int c = D == 128 ? 4 : 2;
-                const int64_t it = ((N + 32 * c - 1) / (32 * c)) * H * B3, nc = (KV + 63) / 64;
-                int64_t want = (cus + it / 2) / it;
-                static const int64_t split_min = getenv("CDNA4_FA_PIPE_SPLIT_MIN") ? atoll(getenv("CDNA4_FA_PIPE_SPLIT_MIN")) : 32;      // (A/B and test knob)
-                if (want > nc / split_min) want = nc / split_min;              // (a split pays from about 32 chunks on: its partial results are written and merged — 512 x 4096 x 32 heads 150 -> 89 us with two splits of 32 chunks, 256 x 2048 46 -> 69 us with four of 8)
-                if (want >= 2) { nw = c; p.chunks_per_split = (int)((nc + want - 1) / want); p.nsplit = (int)((nc + p.chunks_per_split - 1) / p.chunks_per_split); }
-            }
-            if (!nw && D == 128 && KV <= 1024 && ((N + 127) / 128) * H * B3 >= cus / 2) nw = 4;
-        }
-        if (e && getenv("CDNA4_FA_PIPE_SPLIT") && atoi(getenv("CDNA4_FA_PIPE_SPLIT")) > 1) {      // (tests: a forced tile height with a forced key split)
-            const int64_t nc = (KV + 63) / 64, want = std::min<int64_t>(atoi(getenv("CDNA4_FA_PIPE_SPLIT")), nc);
-            p.chunks_per_split = (int)((nc + want - 1) / want); p.nsplit = (int)((nc + p.chunks_per_split - 1) / p.chunks_per_split);
-        }
-        if ((nw == 2 && D == 64) || nw == 4 || nw == 8) {
-            const int64_t qtiles = (N + 32 * nw - 1) / (32 * nw), items = qtiles * H * B3 * p.nsplit;
-            if (p.nsplit > 1) {
-                p.part = (float *)cdna4_gemm_scratch((size_t)(B3 * H * N) * p.nsplit * (D + 4) * 4 + 256, 4);
-                NEED(p.part, "flash_attn_ext: cannot allocate the key-split scratch");
-            }
-            NEED(items < (1ll << 31), "flash_attn_ext: too many query tiles for one grid");
-            NEED(k->nb[1] < (1ll << 25) && v->nb[1] < (1ll << 25) && (!mask || (N + 16) * mask->nb[1] < (1ll << 32)), "flash_attn_ext: row strides beyond the pipelined kernel's 32-bit offsets");
-            // chunks that are -inf throughout for a whole query tile are not walked (k_fa_mask_flags; bit-neutral): worth a pass over the mask from 2^20 entries on
-            // (CDNA4_FA_NO_SKIP / CDNA4_FA_SKIP_MIN: A/B and test knobs)
-            const int64_t nchunk64 = (KV + 63) / 64;
-            NEED(nchunk64 <= 4095, "flash_attn_ext: more than 4095 key chunks");
-            const uint8_t *flags = nullptr;
-            const int64_t skip_min = getenv("CDNA4_FA_SKIP_MIN") ? atoll(getenv("CDNA4_FA_SKIP_MIN")) : (1ll << 20);      // (tests: 0 takes the pass at any size)
-            if (mask && p.mask_vec && N * KV >= skip_min && !getenv("CDNA4_FA_NO_SKIP")) {
-                uint8_t *fl = (uint8_t *)cdna4_gemm_scratch((size_t)(qtiles * nchunk64) + 256, 11);
-                NEED(fl, "flash_attn_ext: cannot allocate the chunk flags");
-                hipLaunchKernelGGL(k_fa_mask_flags, dim3((unsigned)nchunk64, (unsigned)qtiles), dim3(256), 0, st, p, 32 * nw, (int)nchunk64, fl);
-                CDNA4_CHECK_LAUNCH();
-                flags = fl;
-            }
-            const int xcd_map = getenv("CDNA4_FA_MAP") ? atoi(getenv("CDNA4_FA_MAP")) : (mask ? 1 : 0);     // (A/B knob; see the kernel)
-            const int mode = (logit_softcap != 0.0f || !(p.scale > 0.0f) || (mask && !p.mask_vec)) ? 2 : (mask ? 1 : 0);
-#define FA_PIPE3(HS_, NW_, MODE_) do { constexpr int lds_ = k_flash_attn_pipe_lds<HS_, NW_, MODE_>();                                                            \
-                if (lds_ > 64 * 1024) { if (const int rc_ = cdna4_raise_lds_limit<k_flash_attn_pipe<HS_, NW_, MODE_>>(lds_, "flash_attn_ext: cannot raise the dynamic LDS limit")) return rc_; } \
-                hipLaunchKernelGGL((k_flash_attn_pipe<HS_, NW_, MODE_>), dim3((unsigned)items), dim3(64 * NW_), lds_, st, p, (int)qtiles, xcd_map, flags); } while (0)
-#define FA_PIPE(HS_, NW_) do { if (mode == 0) FA_PIPE3(HS_, NW_, 0); else if (mode == 1) FA_PIPE3(HS_, NW_, 1); else FA_PIPE3(HS_, NW_, 2); } while (0)
-            if (D == 64) { if (nw == 8) FA_PIPE(64, 8); else if (nw == 4) FA_PIPE(64, 4); else FA_PIPE(64, 2); }
-            else { if (nw == 8) FA_PIPE(128, 8); else FA_PIPE(128, 4); }
-#undef FA_PIPE3
-#undef FA_PIPE
-            CDNA4_CHECK_LAUNCH();
-            if (p.nsplit > 1) {
-                const dim3 mgrid((unsigned)((N + 31) / 32), (unsigned)H, (unsigned)B3);
-                if (D == 64) hipLaunchKernelGGL(k_flash_attn_pipe_merge<64>, mgrid, dim3(256), 0, st, p);
-                else hipLaunchKernelGGL(k_flash_attn_pipe_merge<128>, mgrid, dim3(256), 0, st, p);
-                CDNA4_CHECK_LAUNCH();
-            }
-            return 0;
-        }
+    for (int i = 0; i < 2; i++) {
+        if (!staged[i]) continue;
+        const T4 *src = i ? v_in : k_in; const size_t bytes = (size_t)(Dp * src->ne[1] * src->ne[2] * src->ne[3]) * 2;
+        NEED(kv[i].data = cdna4_gemm_scratch(bytes + 256, 5 + i), "flash_attn_ext: cannot allocate the fp16 copy of k / v");
+        if (pad && hipMemsetAsync(kv[i].data, 0, bytes, st) != hipSuccess) { (void)hipGetLastError(); return cdna4_set_error_msg("flash_attn_ext: memset failed"); }
+        T4 c = kv[i]; c.ne[0] = D;                                     // head_size columns of rows Dp halves apart
+        if (const int rc = src->type == CDNA4_F16 ? ggml_cdna4_op_cpy(src, &c, 0, stream) : cdna4_launch_to_f16_dense(src, kv[i].data, Dp, st)) return rc;
     }
-    if (fa_takes_wide(N, H, B3)) {                                 // prefill that fills the chip: 128 query rows per work-group, K / V staged through LDS
-        NEED(kvt == CDNA4_F16, "flash_attn_ext: the 128-row kernels take an F16 K / V");
-        const dim3 grid((unsigned)((N + 127) / 128), (unsigned)H, (unsigned)B3);
-        // (head sizes 64 / 128: 64-key chunks; 256: the 32-key-chunk kernel — its forms for the smaller heads were an A/B knob of round 3 and went in round 5)
-        if (D == 64) hipLaunchKernelGGL(k_flash_attn_wide64<64>, grid, dim3(256), 0, st, p);
-        else if (D == 128) hipLaunchKernelGGL(k_flash_attn_wide64<128>, grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(k_flash_attn_wide<256>, grid, dim3(256), 0, st, p);
-        CDNA4_CHECK_LAUNCH();
-        return 0;
+    if (pad) {
+        const size_t nel = (size_t)(Dp * N * H * B3);
+        qq.data = cdna4_gemm_scratch(nel * 4 + 256, 7); dd.data = cdna4_gemm_scratch(nel * 4 + 256, 8);
+        NEED(qq.data && dd.data, "flash_attn_ext: cannot allocate the padded q / dst");
+        if (hipMemsetAsync(qq.data, 0, nel * 4, st) != hipSuccess) { (void)hipGetLastError(); return cdna4_set_error_msg("flash_attn_ext: memset failed"); }
+        T4 c = qq; c.ne[0] = D;
+        if (const int rc = ggml_cdna4_op_cpy(q_in, &c, 0, stream)) return rc;
     }
-    // decode / small batches: 32-row query tiles, the keys split over work-groups until the chip is full (one or two work-groups per CU, below), each split
-    // >= 16 chunks
-    // grouped-query decode: the heads of a K / V head in one tile (k_flash_attn_split; CDNA4_FA_NO_PACK: A/B knob)
-    p.pack = (p.rk2 > 1 && p.rk2 == p.rv2 && N * p.rk2 <= 32 && !getenv("CDNA4_FA_NO_PACK")) ? p.rk2 : 1;
-    const int64_t HT = p.pack > 1 ? H / p.pack : H;                 // tiles along the head axis
-    const int64_t nchunk = (KV + 31) / 32, qtiles = (N + 31) / 32, tiles = qtiles * HT * B3;
-    // work-groups per CU the split aims at: ONE for F16 / BF16 rows (32 K keys x 32 heads 105.6 -> 99.2 us, grouped-query 8 K / V heads 60.6 -> 43.1: fewer partial results to
-    // write, merge and wait for), TWO for quantized rows, whose conversion is VALU work a second resident work-group hides (Q8_0 88.6 against 108.8, Q4_0 66.7 against 81.4)
-    static const int64_t wgs_knob = getenv("CDNA4_FA_SPLIT_WGS") ? atoll(getenv("CDNA4_FA_SPLIT_WGS")) : 0;      // (A/B knob)
-    const int64_t wgs_per_cu = wgs_knob > 0 ? wgs_knob : (kvq ? 2 : 1);
-    int64_t want = (wgs_per_cu * cus + tiles - 1) / tiles;
-    { static const int64_t min_chunks = getenv("CDNA4_FA_SPLIT_MIN") ? atoll(getenv("CDNA4_FA_SPLIT_MIN")) : 16; if (want > nchunk / min_chunks) want = nchunk / min_chunks; }      // (each split at least 16 chunks — four per wave, which the one-chunk-ahead requests need to pay: 4 K keys x 32 heads 26.4 us at 8, 21.3 at 16, 25.4 at 32; CDNA4_FA_SPLIT_MIN: A/B knob)
-    if (want < 1) want = 1;
-    p.chunks_per_split = (int)((nchunk + want - 1) / want);
-    p.nsplit = (int)((nchunk + p.chunks_per_split - 1) / p.chunks_per_split);
-    if (p.nsplit > 1) {
-        p.part = (float *)cdna4_gemm_scratch((size_t)(qtiles * H * B3) * p.nsplit * 32 * (D + 4) * 4 + 256, 4);      // (per HEAD, also when the heads of a group share a tile)
-        NEED(p.part, "flash_attn_ext: cannot allocate the key-split scratch");
-    }
-    const dim3 grid((unsigned)(qtiles * p.nsplit), (unsigned)HT, (unsigned)B3);
-#define FA_SPLIT(T) do { if (D == 64) hipLaunchKernelGGL((k_flash_attn_split<64, T>), grid, dim3(256), 0, st, p); \
-                         else if (D == 128) hipLaunchKernelGGL((k_flash_attn_split<128, T>), grid, dim3(256), 0, st, p); \
-                         else hipLaunchKernelGGL((k_flash_attn_split<256, T>), grid, dim3(256), 0, st, p); } while (0)
-    if (kvt == CDNA4_Q8_0) FA_SPLIT(CDNA4_Q8_0); else if (kvt == CDNA4_Q4_0) FA_SPLIT(CDNA4_Q4_0); else if (kvt == CDNA4_BF16) FA_SPLIT(CDNA4_BF16); else FA_SPLIT(CDNA4_F16);
-#undef FA_SPLIT
-    CDNA4_CHECK_LAUNCH();
-    if (p.nsplit > 1 && N <= 4 && p.nsplit <= 512 && !getenv("CDNA4_FA_MERGE_OLD")) {      // a handful of rows: one work-group per row (CDNA4_FA_MERGE_OLD: A/B knob)
-        const dim3 mgrid((unsigned)N, (unsigned)H, (unsigned)B3);
-        if (D == 64) hipLaunchKernelGGL(k_flash_attn_merge_rows<64>, mgrid, dim3(256), 0, st, p);
-        else if (D == 128) hipLaunchKernelGGL(k_flash_attn_merge_rows<128>, mgrid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(k_flash_attn_merge_rows<256>, mgrid, dim3(256), 0, st, p);
-        CDNA4_CHECK_LAUNCH();
-    } else if (p.nsplit > 1) {
-        const dim3 mgrid((unsigned)qtiles, (unsigned)H, (unsigned)B3);
-        if (D == 64) hipLaunchKernelGGL(k_flash_attn_merge<64>, mgrid, dim3(256), 0, st, p);
-        else if (D == 128) hipLaunchKernelGGL(k_flash_attn_merge<128>, mgrid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(k_flash_attn_merge<256>, mgrid, dim3(256), 0, st, p);
-        CDNA4_CHECK_LAUNCH();
-    }
-    return 0;
+    const int rc = fa_run(pl, q, k, v, mask, d, scale, max_bias, logit_softcap, st);
+    if (rc || !pad) return rc;
+    T4 view = dd; view.ne[0] = D;                                      // the first head_size columns of every padded output row
+    return ggml_cdna4_op_cpy(&view, d_in, 0, stream);
 }

@@ -510,6 +510,126 @@ def test_flash_attn_padded_head_size_with_a_quantized_kv_on_the_cpu():
         assert r[0] < 5e-4 and r[1] is True, (t, D, r)
 
 
+# FLASH_ATTN_EXT launch plans (fattn.hip's fa_make_plan through `fattn_emul plan`).  Shape: "D n_q n_head n_batch n_kv n_head_kv kv_type mask softcap max_bias" (kv_type: 1 F16, 30 BF16,
+# 8 Q8_0, 2 Q4_0, 3 Q4_1; mask: 0 none, 1 rows 16-byte aligned, 2 at a 2-byte offset), 256 CUs.  The expected values are what the launcher did BEFORE it had a plan: recorded from
+# its launches (kernel, grids, LDS bytes, scratch sizes, fattn_params) with the launch calls replaced by prints — not taken from fa_make_plan.
+FATTN_PLAN_TABLE = [
+    # the pipelined kernel: 8 / 4 waves at head size 128, 8 / 4 / 2 at 64; modes 0 (no mask) / 1 (aligned mask) / 2 (softcap, unaligned mask); the flag pass from 2^20 mask entries on
+    ("128 4096 32 1 4096 32 1 1 0 0", "stage=none family=pipe kv_type=1 hs=128 nw=8 mode=1 map=1 nsplit=1 chunks_per_split=128 pack=0 merge=none grid=512,1,1 block=512 lds=139280 mgrid=1,1,1 fgrid=64,16,1 part_bytes=0 flag_bytes=1280"),
+    ("128 4096 32 1 4096 32 1 0 0 0", "stage=none family=pipe kv_type=1 hs=128 nw=8 mode=0 map=0 nsplit=1 chunks_per_split=128 pack=0 merge=none grid=512,1,1 block=512 lds=73744 mgrid=1,1,1 fgrid=1,1,1 part_bytes=0 flag_bytes=0"),
+    ("128 1024 32 1 1024 32 1 1 30 0", "stage=none family=pipe kv_type=1 hs=128 nw=4 mode=2 map=1 nsplit=1 chunks_per_split=32 pack=0 merge=none grid=256,1,1 block=256 lds=73744 mgrid=1,1,1 fgrid=16,8,1 part_bytes=0 flag_bytes=384"),
+    ("128 1024 32 1 1024 8 1 2 0 0", "stage=none family=pipe kv_type=1 hs=128 nw=4 mode=2 map=1 nsplit=1 chunks_per_split=32 pack=0 merge=none grid=256,1,1 block=256 lds=73744 mgrid=1,1,1 fgrid=1,1,1 part_bytes=0 flag_bytes=0"),
+    ("64 4096 32 1 4096 32 1 1 0 0", "stage=none family=pipe kv_type=1 hs=64 nw=8 mode=1 map=1 nsplit=1 chunks_per_split=128 pack=0 merge=none grid=512,1,1 block=512 lds=106512 mgrid=1,1,1 fgrid=64,16,1 part_bytes=0 flag_bytes=1280"),
+    ("64 1024 32 1 2048 32 1 0 0 0", "stage=none family=pipe kv_type=1 hs=64 nw=4 mode=0 map=0 nsplit=1 chunks_per_split=64 pack=0 merge=none grid=256,1,1 block=256 lds=40976 mgrid=1,1,1 fgrid=1,1,1 part_bytes=0 flag_bytes=0"),
+    ("64 512 32 1 512 32 1 1 0 0", "stage=none family=pipe kv_type=1 hs=64 nw=2 mode=1 map=1 nsplit=1 chunks_per_split=16 pack=0 merge=none grid=256,1,1 block=128 lds=57360 mgrid=1,1,1 fgrid=1,1,1 part_bytes=0 flag_bytes=0"),
+    ("64 512 32 1 512 32 1 0 30 0", "stage=none family=pipe kv_type=1 hs=64 nw=2 mode=2 map=0 nsplit=1 chunks_per_split=16 pack=0 merge=none grid=256,1,1 block=128 lds=40976 mgrid=1,1,1 fgrid=1,1,1 part_bytes=0 flag_bytes=0"),
+    ("128 1024 16 2 2048 16 1 1 0 0", "stage=none family=pipe kv_type=1 hs=128 nw=4 mode=1 map=1 nsplit=1 chunks_per_split=64 pack=0 merge=none grid=256,1,1 block=256 lds=106512 mgrid=1,1,1 fgrid=32,8,1 part_bytes=0 flag_bytes=512"),
+    # below one work-group per CU: the smallest tile with the keys split in two (512 x 4096 x 32 heads; its head size 64 twin)
+    ("128 512 32 1 4096 32 1 1 0 0", "stage=none family=pipe kv_type=1 hs=128 nw=4 mode=1 map=1 nsplit=2 chunks_per_split=32 pack=0 merge=pipe grid=256,1,1 block=256 lds=106512 mgrid=16,32,1 fgrid=64,4,1 part_bytes=17301760 flag_bytes=512"),
+    ("64 256 32 1 4096 32 1 0 0 0", "stage=none family=pipe kv_type=1 hs=64 nw=2 mode=0 map=0 nsplit=2 chunks_per_split=32 pack=0 merge=pipe grid=256,1,1 block=128 lds=40976 mgrid=8,32,1 fgrid=1,1,1 part_bytes=4456704 flag_bytes=0"),
+    # KV <= 1024 at head size 128: half a chip of 128-row tiles still takes the pipelined kernel; a quarter does not
+    ("128 512 32 1 1024 32 1 1 0 0", "stage=none family=pipe kv_type=1 hs=128 nw=4 mode=1 map=1 nsplit=1 chunks_per_split=32 pack=0 merge=none grid=128,1,1 block=256 lds=106512 mgrid=1,1,1 fgrid=1,1,1 part_bytes=0 flag_bytes=0"),
+    ("128 512 16 1 1024 16 1 1 0 0", "stage=none family=split kv_type=1 hs=128 nw=0 mode=0 map=0 nsplit=1 chunks_per_split=32 pack=1 merge=none grid=16,16,1 block=256 lds=0 mgrid=1,1,1 fgrid=1,1,1 part_bytes=0 flag_bytes=0"),
+    # head size 256: prefill that fills the chip on the 128-row kernel, smaller prefill on the key-split kernel
+    ("256 1024 32 1 1024 32 1 1 0 0", "stage=none family=wide kv_type=1 hs=256 nw=0 mode=0 map=0 nsplit=1 chunks_per_split=32 pack=0 merge=none grid=8,32,1 block=256 lds=0 mgrid=1,1,1 fgrid=1,1,1 part_bytes=0 flag_bytes=0"),
+    ("256 512 8 1 1024 8 1 1 0 0", "stage=none family=split kv_type=1 hs=256 nw=0 mode=0 map=0 nsplit=2 chunks_per_split=16 pack=1 merge=tiles grid=32,8,1 block=256 lds=0 mgrid=16,8,1 fgrid=1,1,1 part_bytes=8519936 flag_bytes=0"),
+    ("64 33 1 1 4096 1 1 1 0 0", "stage=none family=split kv_type=1 hs=64 nw=0 mode=0 map=0 nsplit=8 chunks_per_split=16 pack=1 merge=tiles grid=16,1,1 block=256 lds=0 mgrid=2,1,1 fgrid=1,1,1 part_bytes=139520 flag_bytes=0"),
+    # one-row decode, without and with grouped-query packing; the row merge up to 4 rows, the tile merge from 5
+    ("128 1 32 1 4096 32 1 1 0 0", "stage=none family=split kv_type=1 hs=128 nw=0 mode=0 map=0 nsplit=8 chunks_per_split=16 pack=1 merge=rows grid=8,32,1 block=256 lds=0 mgrid=1,32,1 fgrid=1,1,1 part_bytes=4325632 flag_bytes=0"),
+    ("128 1 32 1 4096 4 1 1 0 0", "stage=none family=split kv_type=1 hs=128 nw=0 mode=0 map=0 nsplit=8 chunks_per_split=16 pack=8 merge=rows grid=8,4,1 block=256 lds=0 mgrid=1,32,1 fgrid=1,1,1 part_bytes=4325632 flag_bytes=0"),
+    ("128 4 32 1 32768 32 1 1 0 0", "stage=none family=split kv_type=1 hs=128 nw=0 mode=0 map=0 nsplit=8 chunks_per_split=128 pack=1 merge=rows grid=8,32,1 block=256 lds=0 mgrid=4,32,1 fgrid=1,1,1 part_bytes=4325632 flag_bytes=0"),
+    ("128 5 32 1 32768 32 1 1 0 0", "stage=none family=split kv_type=1 hs=128 nw=0 mode=0 map=0 nsplit=8 chunks_per_split=128 pack=1 merge=tiles grid=8,32,1 block=256 lds=0 mgrid=1,32,1 fgrid=1,1,1 part_bytes=4325632 flag_bytes=0"),
+    # a Q8_0 cache: raw under the key-split kernel at 64 query rows, copied to fp16 at 128; Q4_0 (two work-groups per CU) and BF16 decode raw; Q4_1 has no raw form
+    ("128 64 8 1 4096 8 8 1 0 0", "stage=none family=split kv_type=8 hs=128 nw=0 mode=0 map=0 nsplit=8 chunks_per_split=16 pack=1 merge=tiles grid=16,8,1 block=256 lds=0 mgrid=2,8,1 fgrid=1,1,1 part_bytes=2162944 flag_bytes=0"),
+    ("128 128 8 1 4096 8 8 1 0 0", "stage=copy family=pipe kv_type=1 hs=128 nw=4 mode=1 map=1 nsplit=2 chunks_per_split=32 pack=0 merge=pipe grid=16,1,1 block=256 lds=106512 mgrid=4,8,1 fgrid=1,1,1 part_bytes=1081600 flag_bytes=0"),
+    ("128 1 32 1 4096 8 2 1 0 0", "stage=none family=split kv_type=2 hs=128 nw=0 mode=0 map=0 nsplit=8 chunks_per_split=16 pack=4 merge=rows grid=8,8,1 block=256 lds=0 mgrid=1,32,1 fgrid=1,1,1 part_bytes=4325632 flag_bytes=0"),
+    ("64 1 8 1 8192 8 30 0 0 0", "stage=none family=split kv_type=30 hs=64 nw=0 mode=0 map=0 nsplit=16 chunks_per_split=16 pack=1 merge=rows grid=16,8,1 block=256 lds=0 mgrid=1,8,1 fgrid=1,1,1 part_bytes=1114368 flag_bytes=0"),
+    ("64 1 8 1 1024 8 3 1 0 8", "stage=copy family=split kv_type=1 hs=64 nw=0 mode=0 map=0 nsplit=2 chunks_per_split=16 pack=1 merge=rows grid=2,8,1 block=256 lds=0 mgrid=1,8,1 fgrid=1,1,1 part_bytes=139520 flag_bytes=0"),
+    # padded head sizes (80, and 96 with a Q8_0 cache): the head size 128 kernels on zero-padded copies
+    ("80 64 8 1 512 8 1 1 0 0", "stage=pad family=split kv_type=1 hs=128 nw=0 mode=0 map=0 nsplit=1 chunks_per_split=16 pack=1 merge=none grid=2,8,1 block=256 lds=0 mgrid=1,1,1 fgrid=1,1,1 part_bytes=0 flag_bytes=0"),
+    ("96 1 8 1 1024 8 8 1 0 0", "stage=pad family=split kv_type=1 hs=128 nw=0 mode=0 map=0 nsplit=2 chunks_per_split=16 pack=1 merge=rows grid=2,8,1 block=256 lds=0 mgrid=1,8,1 fgrid=1,1,1 part_bytes=270592 flag_bytes=0"),
+]
+
+
+def test_flash_attn_launch_plans_of_a_table_of_shapes():
+    """every routing rule of FLASH_ATTN_EXT at a shape that takes it, with the whole plan the call must get (see FATTN_PLAN_TABLE): staging, kernel family and form, key split,
+    packing, merge kernel, grids, block, dynamic LDS, scratch bytes.  One process, plans only."""
+    plans = _emul_module("fattn_emul_check").plan([tuple(s.split()) for s, _ in FATTN_PLAN_TABLE])
+    for (shape, want), p in zip(FATTN_PLAN_TABLE, plans):
+        assert re.sub(r" chunk=\d+", "", p["line"]) == want, shape
+        assert p["chunk"] == (64 if p["family"] == "pipe" else 32), shape        # keys per chunk of chunks_per_split: the kernels' own constants
+
+
+@pytest.mark.parametrize("cus,env", [(256, {}), (8, {}), (256, {"CDNA4_FA_PIPE": "2", "CDNA4_FA_PIPE_SPLIT": "3"}), (256, {"CDNA4_FA_PIPE": "4", "CDNA4_FA_PIPE_SPLIT": "3", "CDNA4_FA_SKIP_MIN": "0"})])
+def test_flash_attn_launch_plan_properties(cus, env):
+    """what holds for the plan of ANY call, over a grid of some thousand shapes (and under the forced-tile / forced-split knobs, where CDNA4_FA_PIPE=2 names a tile height head
+    size 128 does not have): which kernel may read which K / V, a key split that covers the keys exactly, scratch and merge exactly with a split, LDS and grid limits"""
+    shapes = [(D, nq, h, 1, kv, hk, t, m, sc, 0) for D in (64, 80, 128, 256) for nq in (1, 4, 5, 32, 33, 127, 128, 512, 4096) for kv in (96, 1024, 4096, 32768)
+              for h, hk in ((1, 1), (8, 1), (32, 32)) for t in (1, 30, 8, 2, 3) for m, sc in ((0, 0), (1, 0), (2, 0), (1, 30)) if D % 32 == 0 or t in (1, 30)]
+    shapes += [(128, nq, 1, 1, 1 << 20, 1, t, 1, 0, 0) for nq in (1, 4, 5) for t in (1, 2)]      # (a million keys under one head: more than 512 splits on a chip of 2048 CUs, below)
+    assert len(shapes) > 5000
+    plans = _emul_module("fattn_emul_check").plan(shapes, cus=cus, env=env) + _emul_module("fattn_emul_check").plan(shapes[-6:], cus=2048, env=env)
+    seen = set()
+    for s, p in zip(shapes + shapes[-6:], plans):
+        D, nq, kv, t = s[0], s[1], s[4], s[6]
+        why = (s, p["line"])
+        seen.add((p["family"], p["stage"], p["merge"], p["nw"], p["nsplit"] > 512))
+        assert (p["stage"] == "pad") == (D == 80) and p["hs"] == (128 if D == 80 else D), why
+        if p["family"] == "pipe":
+            assert p["kv_type"] == 1 and p["hs"] in (64, 128) and nq > 32 and p["nw"] in ((2, 4, 8) if p["hs"] == 64 else (4, 8)) and p["block"] == 64 * p["nw"], why
+        assert p["kv_type"] in (1, t), why
+        if p["kv_type"] != 1:                                            # a raw BF16 / Q8_0 / Q4_0 cache: the key-split kernel alone reads it, and only below 128 query rows
+            assert p["family"] == "split" and nq < 128 and p["stage"] == "none" and t in (30, 8, 2), why
+        assert (p["stage"] == "copy") == (D != 80 and t != 1 and p["kv_type"] == 1), why
+        nchunk = -(-kv // p["chunk"])
+        assert p["nsplit"] >= 1 and (p["nsplit"] - 1) * p["chunks_per_split"] < nchunk <= p["nsplit"] * p["chunks_per_split"], why
+        if p["family"] == "wide":
+            assert p["nsplit"] == 1 and p["kv_type"] == 1, why
+        assert (p["part_bytes"] > 0) == (p["nsplit"] > 1) == (p["merge"] != "none"), why
+        assert (p["merge"] == "pipe") == (p["family"] == "pipe" and p["nsplit"] > 1), why
+        assert (p["merge"] == "rows") == (p["nsplit"] > 1 and nq <= 4 and p["nsplit"] <= 512), why
+        assert 0 <= p["lds"] <= 160 * 1024 and (p["lds"] > 0) == (p["family"] == "pipe"), why
+        for g in (p["grid"], p["mgrid"], p["fgrid"]):
+            assert 0 < g[0] < 2 ** 31 and 0 < g[1] <= 65535 and 0 < g[2] <= 65535, why
+    if not env:                                                          # the grid reaches what the properties speak of
+        assert {f for f, *_ in seen} == {"pipe", "wide", "split"} and {m for _, _, m, *_ in seen} == {"none", "tiles", "rows", "pipe"} and {st for _, st, *_ in seen} == {"none", "copy", "pad"}, seen
+        assert any(big for *_, big in seen), seen
+    if env.get("CDNA4_FA_PIPE") == "2":                                  # head size 128 has no 2-wave form: those calls take the older kernels, unsplit where that is a 128-row kernel
+        assert ("wide", "none", "none", 0, False) in seen and not any(f == "pipe" and nw != 2 for f, _, _, nw, _ in seen), seen
+
+
+# calls FLASH_ATTN_EXT must refuse: (D_q, D_k, D_v, D_dst, n_q, n_head, n_kv, n_head_kv, kv_type, mask, max_bias, k_offset) and the message — those of the launcher before it had a plan
+FATTN_REJECTED = [
+    ((128, 128, 128, -1, 64, 8, 512, 8, 1, 1, 0, 0), "flash_attn_ext: q, k, v and dst are required"),
+    ((0, 0, 0, 0, 64, 8, 512, 8, 1, 1, 0, 0), "flash_attn_ext: head size must be 1..256"),
+    ((300, 300, 300, 300, 64, 8, 512, 8, 1, 1, 0, 0), "flash_attn_ext: head size must be 1..256"),
+    ((128, 128, 128, 128, 64, 8, 0, 8, 1, 1, 0, 0), "flash_attn_ext: no keys"),
+    ((128, 128, 128, 128, 64, 8, 512, 8, 1, 3, 0, 0), "flash_attn_ext: mask must be F16 [n_kv, >= n_q]"),
+    ((128, 128, 128, 128, 64, 8, 512, 8, 1, 0, 8, 0), "flash_attn_ext: ALiBi needs a mask"),
+    ((128, 128, 128, 128, 1, 65536, 512, 65536, 1, 1, 0, 0), "flash_attn_ext: too many heads / batches for one grid"),
+    ((128, 128, 128, 128, 64, 8, 512, 8, 1, 1, 0, 2), "flash_attn_ext: k / v rows and dst must be 16-byte aligned"),
+    ((128, 128, 128, 128, 64, 8, 512, 3, 1, 1, 0, 0), "flash_attn_ext: heads / batch not broadcastable over k / v"),
+    ((128, 128, 128, 128, 64, 8, 512, 8, 12, 1, 0, 0), "flash_attn_ext: k / v must be F16, BF16 or Q4_0 / Q4_1 / Q5_0 / Q5_1 / Q8_0"),
+    # q's head size against that of k, v and dst, on every staging: nothing staged (F16, raw Q8_0), fp16 copy (Q4_1), padded
+    ((64, 128, 128, 128, 1, 8, 64, 8, 1, 1, 0, 0), "flash_attn_ext: k / v shape mismatch"),
+    ((64, 128, 128, 128, 1, 8, 64, 8, 8, 1, 0, 0), "flash_attn_ext: k / v shape mismatch"),
+    ((64, 100, 100, 100, 64, 8, 512, 8, 1, 1, 0, 0), "flash_attn_ext: k / v shape mismatch"),
+    ((128, 64, 128, 128, 64, 8, 512, 8, 1, 1, 0, 0), "flash_attn_ext: k / v shape mismatch"),
+    ((128, 128, 64, 128, 64, 8, 512, 8, 1, 1, 0, 0), "flash_attn_ext: k / v shape mismatch"),
+    ((128, 128, 128, 64, 64, 8, 512, 8, 1, 1, 0, 0), "flash_attn_ext: dst must be [head_size, n_head, n_q, batch]"),
+    ((64, 128, 128, 128, 1, 8, 64, 8, 3, 1, 0, 0), "flash_attn_ext: bad k / v shape"),
+    ((80, 128, 80, 80, 64, 8, 512, 8, 1, 1, 0, 0), "flash_attn_ext: bad k / v shape"),
+    ((80, 80, 80, 128, 64, 8, 512, 8, 1, 1, 0, 0), "flash_attn_ext: dst must be [head_size, n_head, n_q, batch]"),
+]
+
+
+def test_flash_attn_refuses_invalid_calls_before_any_launch():
+    """ggml_cdna4_op_flash_attn_ext itself (the checks in front of the plan's execution) on operands without memory behind them: every call of FATTN_REJECTED
+    returns -1 with its message, and none reaches a kernel (which would end the harness with a fault)"""
+    got = _emul_module("fattn_emul_check").reject([c for c, _ in FATTN_REJECTED])
+    assert got == [(-1, m) for _, m in FATTN_REJECTED], [(c, g, m) for (c, m), g in zip(FATTN_REJECTED, got) if g != (-1, m)]
+
+
 def test_hardware_verified_kernels_are_unchanged():
     """tools/isa_manifest.py: the ISA of every kernel that was part of a build with a green hardware session (profiles/rNN/isa_manifest.json,
     `hw`: true) is what hipcc emits for it today — so what was added since (listed there as `hw`: false, or new) cannot have changed the

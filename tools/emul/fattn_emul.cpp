@@ -1,6 +1,11 @@
 // fattn_emul.cpp — runs the SOURCE of the FLASH_ATTN_EXT kernels (ggml_amd/csrc/fattn.hip: k_flash_attn_split / _merge / _wide <64 / 128 / 256>) on the CPU, one OS
 // thread per GPU thread, the 32x32x16 fp16 MFMA emulated lane for lane (hip_emul.h).  Test infrastructure.
 //   fattn_emul D n_q n_head n_batch n_kv n_head_kv n_batch_kv has_mask mask_rows scale max_bias softcap permuted q.bin k.bin v.bin mask.bin out.bin [kv_type]
+//   fattn_emul plan < shapes     one line per call, "D n_q n_head n_batch n_kv n_head_kv kv_type mask softcap max_bias" (mask: 0 none, 1 rows 16-byte aligned, 2 at a 2-byte
+//                                offset): prints the launch plan of each (fa_make_plan: what the call would stage and launch) and runs no kernel
+//   fattn_emul reject < calls    one line per call that ggml_cdna4_op_flash_attn_ext must refuse, "D_q D_k D_v D_dst n_q n_head n_kv n_head_kv kv_type mask max_bias k_offset" (D_dst -1: no
+//                                dst; mask 3: one column too many; k_offset: bytes added to K's address): prints "rc message" of each.  The operands are addresses without
+//                                memory: a call that got as far as a kernel would end the run with a fault
 // kv_type (default 1 = F16): a ggml block type (2, 3, 6, 7, 8) makes k.bin / v.bin block-quantized rows (the conversion pass in front of the kernels runs too)
 // q f32 [n_batch][n_head][n_q][D] (permuted = 1: stored [n_batch][n_q][n_head][D] and described through strides, like the stock test's
 // ggml_permute(0, 2, 1, 3) case; likewise k / v), k / v fp16, mask fp16 [mask_rows][n_kv]; out f32 [n_batch][n_q][n_head][D]
@@ -23,7 +28,8 @@ bool g_defer_dma = false;
 size_t g_weaken = 0;
 }
 __attribute__((aligned(16))) uint8_t fa_dyn_lds[160 * 1024];           // the dynamic LDS of k_flash_attn_pipe (a work-group is a process: one array)
-int cdna4_set_error_msg(const char *m) { fprintf(stderr, "error: %s\n", m); return -1; }
+static const char *g_last_error = "";
+int cdna4_set_error_msg(const char *m) { g_last_error = m; fprintf(stderr, "error: %s\n", m); return -1; }
 int cdna4_set_error(hipError_t, const char *, int) { return -1; }
 static void *shared_alloc(size_t n) {                                  // between two inaccessible pages: an out-of-bounds access kills the work-group
     const size_t pg = 4096, body = (n + pg - 1) / pg * pg;
@@ -81,11 +87,57 @@ static inline hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t) {
 #undef NEED
 #include "../../ggml_amd/csrc/fattn.hip"
 
+static void fill(ggml_cdna4_tensor &t, void *data, int type, int64_t es, int64_t n0, int64_t n1, int64_t n2, int64_t n3, bool perm) {
+    t.data = data; t.type = type; t.ne[0] = n0; t.ne[1] = n1; t.ne[2] = n2; t.ne[3] = n3;
+    t.nb[0] = es; t.nb[3] = es * n0 * n1 * n2;
+    if (!perm) { t.nb[1] = es * n0; t.nb[2] = es * n0 * n1; } else { t.nb[2] = es * n0; t.nb[1] = es * n0 * n2; }      // memory order [n3][n1][n2][n0]
+}
+static int plan_mode() {
+    static const char *stage[] = {"none", "copy", "pad"}, *family[] = {"pipe", "wide", "split"}, *merge[] = {"none", "tiles", "rows", "pipe"};
+    char line[512];
+    while (fgets(line, sizeof line, stdin)) {
+        long long D, NQ, H, B3, KV, HK; int kvt, mask; float softcap, max_bias;
+        if (sscanf(line, "%lld %lld %lld %lld %lld %lld %d %d %f %f", &D, &NQ, &H, &B3, &KV, &HK, &kvt, &mask, &softcap, &max_bias) != 10) { fprintf(stderr, "bad shape line: %s", line); return 2; }
+        const bool plain = kvt == CDNA4_F16 || kvt == CDNA4_BF16;
+        const int64_t kes = plain ? 2 : (int64_t)tsize(kvt), kn0 = plain ? D : D / bsize(kvt);
+        ggml_cdna4_tensor tq{}, tk{}, tv{}, tm{};
+        char *base = (char *)(uintptr_t)(1ull << 40);                  // descriptors only: nothing is read
+        fill(tq, base, CDNA4_F32, 4, D, NQ, H, B3, false); fill(tk, base, kvt, kes, kn0, KV, HK, B3, false); fill(tv, base, kvt, kes, kn0, KV, HK, B3, false);
+        tk.ne[0] = tv.ne[0] = D;
+        if (mask) fill(tm, base + (mask == 2 ? 2 : 0), CDNA4_F16, 2, KV, (NQ + 63) / 64 * 64, 1, 1, false);
+        const fa_plan p = fa_make_plan(&tq, &tk, &tv, mask ? &tm : nullptr, softcap == 0.0f);
+        printf("stage=%s family=%s kv_type=%d hs=%d nw=%d mode=%d map=%d nsplit=%d chunks_per_split=%d chunk=%d pack=%d merge=%s grid=%u,%u,%u block=%d lds=%d mgrid=%u,%u,%u fgrid=%u,%u,%u part_bytes=%zu flag_bytes=%zu\n",
+               stage[p.stage], family[p.family], p.kv_type, p.hs, p.nw, p.mode, p.xcd_map, p.nsplit, p.chunks_per_split, p.chunk, p.pack, merge[p.merge], p.grid.x, p.grid.y, p.grid.z, p.block, p.lds,
+               p.mgrid.x, p.mgrid.y, p.mgrid.z, p.fgrid.x, p.fgrid.y, p.fgrid.z, p.part_bytes, p.flag_bytes);
+    }
+    return 0;
+}
+static int reject_mode() {
+    char line[512];
+    while (fgets(line, sizeof line, stdin)) {
+        long long Dq, Dk, Dv, Dd, NQ, H, KV, HK, koff; int kvt, mask; float max_bias;
+        if (sscanf(line, "%lld %lld %lld %lld %lld %lld %lld %lld %d %d %f %lld", &Dq, &Dk, &Dv, &Dd, &NQ, &H, &KV, &HK, &kvt, &mask, &max_bias, &koff) != 12) { fprintf(stderr, "bad call line: %s", line); return 2; }
+        const bool plain = kvt == CDNA4_F16 || kvt == CDNA4_BF16;
+        const int64_t kes = plain ? 2 : (int64_t)tsize(kvt), kb = plain ? 1 : bsize(kvt);
+        ggml_cdna4_tensor tq{}, tk{}, tv{}, tm{}, td{};
+        char *base = (char *)(uintptr_t)(1ull << 40);
+        fill(tq, base, CDNA4_F32, 4, Dq, NQ, H, 1, false); fill(tk, base + koff, kvt, kes, Dk / kb, KV, HK, 1, false); fill(tv, base, kvt, kes, Dv / kb, KV, HK, 1, false);
+        tk.ne[0] = Dk; tv.ne[0] = Dv;
+        if (mask) fill(tm, base, CDNA4_F16, 2, KV + (mask == 3), (NQ + 63) / 64 * 64, 1, 1, false);
+        fill(td, base, CDNA4_F32, 4, Dd, H, NQ, 1, false);
+        g_last_error = "";
+        const int rc = ggml_cdna4_op_flash_attn_ext(&tq, &tk, &tv, mask ? &tm : nullptr, Dd < 0 ? nullptr : &td, 0.125f, max_bias, 0.0f, nullptr);
+        printf("%d %s\n", rc, g_last_error); fflush(stdout);
+    }
+    return 0;
+}
 static void slurp(const char *p, void *dst, size_t n) {
     FILE *f = fopen(p, "rb"); if (!f || fread(dst, 1, n, f) != n) { perror(p); exit(2); } fclose(f);
 }
 int main(int argc, char **argv) {
     emu::g_defer_dma = getenv("EMU_DEFER_DMA") && atoi(getenv("EMU_DEFER_DMA")) != 0;
+    if (argc == 2 && !strcmp(argv[1], "plan")) return plan_mode();
+    if (argc == 2 && !strcmp(argv[1], "reject")) return reject_mode();
     if (argc < 19) { fprintf(stderr, "usage: fattn_emul D n_q n_head n_batch n_kv n_head_kv n_batch_kv has_mask mask_rows scale max_bias softcap permuted q k v mask out\n"); return 2; }
     const int64_t D = atoll(argv[1]), NQ = atoll(argv[2]), H = atoll(argv[3]), B3 = atoll(argv[4]), KV = atoll(argv[5]), HK = atoll(argv[6]), BK = atoll(argv[7]);
     const int has_mask = atoi(argv[8]); const int64_t MR = atoll(argv[9]);
@@ -97,11 +149,6 @@ int main(int argc, char **argv) {
     slurp(argv[14], q, nq); slurp(argv[15], k, nk); slurp(argv[16], v, nk); if (has_mask) slurp(argv[17], m, nm);
     memset(o, 0xFF, no);
     ggml_cdna4_tensor tq{}, tk{}, tv{}, tm{}, td{};
-    auto fill = [&](ggml_cdna4_tensor &t, void *data, int type, int64_t es, int64_t n0, int64_t n1, int64_t n2, int64_t n3, bool perm) {
-        t.data = data; t.type = type; t.ne[0] = n0; t.ne[1] = n1; t.ne[2] = n2; t.ne[3] = n3;
-        t.nb[0] = es; t.nb[3] = es * n0 * n1 * n2;
-        if (!perm) { t.nb[1] = es * n0; t.nb[2] = es * n0 * n1; } else { t.nb[2] = es * n0; t.nb[1] = es * n0 * n2; }      // memory order [n3][n1][n2][n0]
-    };
     fill(tq, q, CDNA4_F32, 4, D, NQ, H, B3, permuted); fill(tk, k, kvt, kes, kn0, KV, HK, BK, permuted); fill(tv, v, kvt, kes, kn0, KV, HK, BK, permuted);
     tk.ne[0] = tv.ne[0] = D;                                            // (fill() computed the strides from blocks per row)
     if (has_mask) fill(tm, m, CDNA4_F16, 2, KV, MR, 1, 1, false);

@@ -103,6 +103,35 @@ def run_quantized(t, D, n_q, n_head, n_kv, n_head_kv=None, permuted=False, seed=
     return R.rel_l2(outs[0], R.exact_flash_attn_ext(q, kf, vf, m, scale)), bool(np.array_equal(outs[0], outs[1]))
 
 
+def plan(shapes, cus=256, env=None):
+    """the launch plans of calls (fattn.hip's fa_make_plan through `fattn_emul plan`: no kernel runs).  shapes: tuples
+    (D, n_q, n_head, n_batch, n_kv, n_head_kv, kv_type, mask, softcap, max_bias) with mask 0 = none, 1 = rows 16-byte aligned, 2 = at a 2-byte offset;
+    env: CDNA4_FA_* knobs.  Returns one dict per shape (numbers as int, grids as tuples), its `line` being the text the harness printed"""
+    r = subprocess.run([build(), "plan"], input="".join(" ".join(str(x) for x in s) + "\n" for s in shapes), capture_output=True, text=True, timeout=120,
+                       env=dict({k: v for k, v in os.environ.items() if not k.startswith("CDNA4_FA_")}, EMU_CUS=str(cus), **(env or {})))
+    assert r.returncode == 0, r.stderr
+    lines = r.stdout.splitlines()
+    assert len(lines) == len(shapes), (len(lines), len(shapes))
+    out = []
+    for line in lines:
+        d = {"line": line}
+        for k, v in (f.split("=") for f in line.split()):
+            d[k] = tuple(int(x) for x in v.split(",")) if "," in v else (int(v) if v.lstrip("-").isdigit() else v)
+        out.append(d)
+    return out
+
+
+def reject(calls, cus=256):
+    """what ggml_cdna4_op_flash_attn_ext answers to calls it must refuse (`fattn_emul reject`): calls are tuples (D_q, D_k, D_v, D_dst, n_q, n_head, n_kv, n_head_kv, kv_type, mask,
+    max_bias, k_offset) — see fattn_emul.cpp.  Returns one (return code, message) per call; a call that reached a kernel ends the harness with a fault, which fails here"""
+    r = subprocess.run([build(), "reject"], input="".join(" ".join(str(x) for x in c) + "\n" for c in calls), capture_output=True, text=True, timeout=120,
+                       env=dict({k: v for k, v in os.environ.items() if not k.startswith("CDNA4_FA_")}, EMU_CUS=str(cus)))
+    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    out = [(int(ln.split(" ", 1)[0]), ln.split(" ", 1)[1]) for ln in r.stdout.splitlines()]
+    assert len(out) == len(calls), (out, r.stderr)
+    return out
+
+
 if __name__ == "__main__":
     D, nq, nh, nkv = (int(a) for a in sys.argv[1:5]) if len(sys.argv) > 4 else (64, 5, 2, 96)
     print("flash-attn source on the CPU, D=%d n_q=%d n_head=%d n_kv=%d: rel-L2 vs float64 / vs oracle =" % (D, nq, nh, nkv), run(D, nq, nh, nkv))
