@@ -3,6 +3,7 @@
 #include "cdna4_common.h"
 #include "cdna4_formats.hpp"
 #include "cdna4_kernels.h"
+#include "gemm_q_plan.hpp"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -338,13 +339,14 @@ static mm_plan plan_mul_mat(int type, const void *W, int64_t w_row_bytes, const 
         else { p.kind = X && cdna4_gemv_staged_supported(type, K, B) ? MM_GEMV_STAGED : MM_GEMV; p.route_id = 2; }
         return p;
     }
-    // the GEMM side's single source of truth is its launcher, run with a probe armed (gemm_q_mfma.hip): it sees W's alignment and resident image, the
+    // the GEMM side's single source of truth is the plan its launcher executes (gemm_q_plan.hpp): it sees W's alignment and resident image, the
     // image's alignment and, where the call hands its fp32 rows over next to a usable workspace, whether ONE launch does the whole step
     const void *xh = carve(type, K, B, (void *)workspace).xh;
     cdna4_gemm_args a = gemm_args_of(type, W, w_row_bytes, xh, nullptr, 0, M, K, B, gemm_variant, splitk, cdna4_epilogue{});
     if (X && workspace && !((uintptr_t)workspace & 255)) { a.xf = X; a.xf_row_elems = x_row_stride; }
-    p.kind = cdna4_gemm_q_fuses_quantizer(a) ? MM_GEMM_1 : MM_GEMM;
-    p.route_id = cdna4_gemm_q_route(a); p.image_key = key | 16u; p.tail_in_store = cdna4_gemm_q_fuses_tail(a);
+    const gemm_q_plan g = gemm_q_make_plan(a);
+    p.kind = g.fuses_quantizer ? MM_GEMM_1 : MM_GEMM;
+    p.route_id = gemm_q_route_id(g); p.image_key = key | 16u; p.tail_in_store = g.tail_in_store;
     return p;
 }
 // the plan of the AUTO call on contiguous, 256-byte-aligned activations and workspace: what the queries answer from

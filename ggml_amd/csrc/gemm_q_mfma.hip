@@ -13,7 +13,7 @@
 //    nibble unpack needs no byte shuffles (see chunk_of() and the pair-interleaved, k-panel-major fp16 image);
 //  * packed weights and fp16 activations are staged through a 3-slot LDS ring (global_load_lds_dwordx4, 16-byte chunks
 //    XOR-swizzled on the SOURCE address so the fragment ds_read_b128s are conflict-free); XCD-aware tile order.
-// Kernels, oldest to newest (launch_type() picks; DESIGN.md 4.3 has the measurements):
+// Kernels, oldest to newest (gemm_q_make_plan() picks; DESIGN.md 4.3 has the measurements):
 //    k_gemm_q        4 waves, slice-per-barrier, per-lane weight loads, 128-wide activation tile — any format; K % 256 != 0, and (IDS) the grouped MUL_MAT_ID of Q5_K / Q6_K / Q4_0 / Q8_0
 //    k_gemm_kq_w8    8 waves (two per SIMD), 128x128 tile, in-wave unpack/MFMA pipeline, split-K = 2 exchange — the shallow-K (< 3 superblocks per work-group) form of the next two
 //    k_gemm_kq_w8p   + cross-stage software pipeline (barrier in the middle of the MFMA stream)   (Q5_K default)
@@ -21,6 +21,7 @@
 //    (huge grids: k_gemm_kq_t64<.., 256> of gemm_q_t64.hip)
 //    k_repack_*      16-byte-aligned re-layout of Q4_0 / Q8_0 / Q6_K into scratch (shallow-K fallback of the staged path)
 #include "gemm_q_common.h"
+#include "gemm_q_plan.hpp"
 #include "cdna4_formats.hpp"
 #include <atomic>
 #include <mutex>
@@ -452,57 +453,80 @@ int cdna4_gemm_take_fault(bool clear) {
 }
 static int co_cus() { return cdna4_gemm_coresident_cus(); }
 
-// Route probe (the tail predictor must not be a hand-kept copy of the routing): cdna4_gemm_q_fuses_tail() runs the SAME routing code with the
-// probe armed; every route ends in ROUTE_END(does this kernel apply a.epi in its store?) in front of its first side effect (scratch, zero-fill, launch).
-static thread_local struct { bool active, fuses; int kernel, reencoded; bool fuseq; } g_probe = {false, false, 0, 0, false};
+// ---- The routing plan (gemm_q_plan.hpp; ADVICE r3: the tail predictor must not be a hand-kept copy of the routing): gemm_q_make_plan() below decides, side-effect free, which
+// kernel a call takes, where its weights come from and the terminal's launch parameters; cdna4_launch_gemm_q() executes that plan, the queries read its fields.
 // kernel ids (ggml_cdna4_mul_mat_route, include/ggml_cdna4.h): 10 k_gemm_kq_t64, 12 k_gemm_r8, 13 the 128 x 128-tile kernels (k_gemm_kq_w8 / _w8p / _w12), 14 the older per-lane-load
 // kernel (k_gemm_q)
-#define ROUTE_END_K(f, kid) do { if (g_probe.active) { g_probe.fuses = (f); g_probe.kernel = (kid); return 0; } } while (0)
-#define ROUTE_END(f) ROUTE_END_K(f, 0)
 
-template <int TYPE>
-static int launch_w8(const cdna4_gemm_args &a, int splitk, int opt, hipStream_t st, int exp = 0) {
-    gemm_params p{}; p.trace = nullptr; p.partial = nullptr; p.flags = nullptr; p.sb_split = 0;
-    p.W = a.W; p.w_row_bytes = a.w_row_bytes; p.xh = (const half_t *)a.xh; p.xh_row = a.xh_row_elems;
-    p.Y = a.Y; p.y_row = a.y_row_elems; p.M = a.M; p.K = a.K; p.B = a.B; p.splitk = splitk;
-    p.tiles_m = (a.M + 127) / 128; p.tiles_b = (a.B + 127) / 128;
-    p.partial = nullptr; p.flags = nullptr;
-    p.epi = a.epi;                                                        // gemm_w8_epilogue.inc applies it in the tile's store (not on the atomic-sum path)
-    const int ntiles = p.tiles_m * p.tiles_b;
+// experiment bits of k_gemm_kq_w12 (variant bits 16+), built in -DCDNA4_ABLATIONS libraries (tools/microbench) only: 1 = early table read (bit-identical, measured: no gain),
+// 16.. = timing-only ablations
+#ifdef CDNA4_ABLATIONS
+#define W12_EXPS(X) X(1) X(2) X(4) X(6) X(16) X(32) X(64) X(128) X(256) X(96) X(224) X(480) X(288) X(512) X(544) X(992)
+#else
+#define W12_EXPS(X)
+#endif
+static bool w12_exp_built(int exp) {
+#define W12_CASE(E) case E:
+    switch (exp) { case 0: W12_EXPS(W12_CASE) return true; default: return false; }
+#undef W12_CASE
+}
+
+// the 128 x 128-tile kernels on `type` (the kernel's own format: 100.. re-laid, 200.. staged): split, exchange and schedule for the chosen splitk / opt (65 k_gemm_kq_w12,
+// 64 k_gemm_kq_w8p, else the schedule option of k_gemm_kq_w8).  a.splitk is the CALLER's (also behind a re-encoding): AUTO or explicit
+static const char *w8_make_plan(int type, const cdna4_gemm_args &a, int splitk, int opt, int exp, w8_plan &w) {
+    const int tiles_b = (a.B + 127) / 128, ntiles = ((a.M + 127) / 128) * tiles_b, total = a.K / 256;
     // split in two: AUTO (a.splitk <= 0) takes the TICKETED sum of gemm_w8_epilogue.inc (the last of a tile's two work-groups adds both partial tiles; nobody
     // waits, no co-residency assumed — round 4); an explicit splitk = 2 keeps the spinning hand-off where both halves of every tile are resident at once, and
     // falls back to a zero fill + fp32 atomics otherwise
     static const bool handoff_env = getenv("CDNA4_W8_HANDOFF") && atoi(getenv("CDNA4_W8_HANDOFF")) != 0;     // (A/B: the spinning hand-off for AUTO splits too)
-    const bool ticketed = splitk == 2 && a.splitk <= 0 && (size_t)ntiles <= 8192 && !handoff_env;
-    const bool exchange = ticketed || (splitk == 2 && ntiles * 2 <= co_cus());
-    ROUTE_END_K(splitk == 1 || exchange, 13);
-    if (splitk > 1 && !exchange) p.epi = cdna4_epilogue{};
-    if (exchange) {
+    w.type = type; w.splitk = splitk; w.exp = exp; w.sb_split = 0; w.xchg_l2 = 0;
+    w.ticketed = splitk == 2 && a.splitk <= 0 && (size_t)ntiles <= 8192 && !handoff_env;
+    w.exchange = w.ticketed || (splitk == 2 && ntiles * 2 <= co_cus());
+    if (w.exchange) {
+        // the exchange is symmetric (each work-group exports half of its partial tile and finishes the other half): even split, the odd superblock to ks = 0
+        const int split = (total + 1) / 2;
+        w.sb_split = split < 1 ? 1 : (split > total - 1 ? total - 1 : split);
+        // both work-groups of a tile share an XCD iff the XCD-aware remap is active (grid % 8 == 0) and each XCD's slice of the
+        // tile order holds whole (tile_b x ks) groups; work-groups go to XCDs round-robin by blockIdx (the kernel verifies it)
+        const int nb = ntiles * splitk;
+        w.xchg_l2 = ((nb & 7) == 0 && ((nb >> 3) % (tiles_b * 2)) == 0) ? 1 : 0;
+    }
+    // the cross-stage pipeline is written for K ranges of >= 3 superblocks per work-group; shallower ones take schedule 20
+    const int min_nsb = w.exchange ? (w.sb_split < total - w.sb_split ? w.sb_split : total - w.sb_split) : total / splitk;
+    w.opt = ((opt == 64 || opt == 65) && min_nsb < 3) ? 20 : opt;
+    // (what a type cannot reach is not instantiated: the re-laid formats (100..) never take the loader-wave kernel, the staged ones (200..) take nothing else — round 5: 9 kernels)
+    if (type >= 100 && type < 200) { if (w.opt == 65) return "gemm_q: the re-laid formats run on k_gemm_kq_w8p / _w8"; }      // (any other option: k_gemm_kq_w8p, or schedule 20)
+    else if (w.opt == 65) { if (type == CDNA4_Q4_K && !w12_exp_built(exp)) return "gemm_q: this k_gemm_kq_w12 experiment is not built"; }
+    else if (type >= 200) return "gemm_q: staged formats run on the loader-wave kernel only";
+    else if (w.opt != 64 && (w.opt & 31) != 20) return "gemm_q: of the 8-wave in-wave schedules only option 20 is built (variant 663)";
+    return nullptr;
+}
+
+template <int TYPE>
+static int launch_w8(const cdna4_gemm_args &a, const w8_plan &w, hipStream_t st) {
+    gemm_params p{};
+    p.W = a.W; p.w_row_bytes = a.w_row_bytes; p.xh = (const half_t *)a.xh; p.xh_row = a.xh_row_elems;
+    p.Y = a.Y; p.y_row = a.y_row_elems; p.M = a.M; p.K = a.K; p.B = a.B; p.splitk = w.splitk;
+    p.tiles_m = (a.M + 127) / 128; p.tiles_b = (a.B + 127) / 128;
+    p.sb_split = w.sb_split; p.xchg_l2 = w.xchg_l2;
+    const int ntiles = p.tiles_m * p.tiles_b;
+    if (w.splitk == 1 || w.exchange) p.epi = a.epi;                       // gemm_w8_epilogue.inc applies it in the tile's store (not on the atomic-sum path)
+    if (w.exchange) {
         // exchange slots after a FIXED 64-KB flag area (so that no shape's slots ever overlay another shape's flags).  A flag is
         // non-zero only between its writer's publication and its reader's reset inside one launch: no per-launch state on the
         // host, so the launch is graph-capturable once the scratch exists.
-        const size_t pbytes = (size_t)ntiles * 128 * 128 * 4 * (ticketed ? 2 : 1), fbytes = 65536;      // hand-off: two half tiles per tile; ticketed: two whole ones
+        const size_t pbytes = (size_t)ntiles * 128 * 128 * 4 * (w.ticketed ? 2 : 1), fbytes = 65536;      // hand-off: two half tiles per tile; ticketed: two whole ones
         char *sc = (char *)get_scratch(fbytes + pbytes);
         if (!sc) return cdna4_set_error_msg("gemm_q: cannot allocate split-K scratch");
         p.flags = (unsigned *)sc; p.partial = (float *)(sc + fbytes);
-        // the exchange is symmetric (each work-group exports half of its partial tile and finishes the other half): even split,
-        // the odd superblock to ks = 0
-        const int total = a.K / 256;
-        int split = (total + 1) / 2;
-        p.sb_split = split < 1 ? 1 : (split > total - 1 ? total - 1 : split);
-    } else if (splitk > 1) {
+    } else if (w.splitk > 1) {
         const int64_t n = (int64_t)a.M * a.B;
         hipLaunchKernelGGL(k_zero_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.Y, a.y_row_elems, a.M, a.B);
     }
     p.trace = (unsigned long long *)cdna4_debug_trace;
-    {   // both work-groups of a tile share an XCD iff the XCD-aware remap is active (grid % 8 == 0) and each XCD's slice of the
-        // tile order holds whole (tile_b x ks) groups; work-groups go to XCDs round-robin by blockIdx (the kernel verifies it)
-        const int nb = p.tiles_m * p.tiles_b * splitk;
-        p.xchg_l2 = (p.partial && (nb & 7) == 0 && ((nb >> 3) % (p.tiles_b * 2)) == 0) ? 1 : 0;
-    }
-    if (exchange && !ticketed) p.fault = cdna4_gemm_fault_word();         // (the waiting hand-off)
-    p.tune = ticketed ? 2 : 0;      // bit1 = the ticketed split (gemm_w8_epilogue.inc); (bit0 = s_setprio 1 for the later-dispatched khalf-1 waves of k_gemm_kq_w8p: measured 26.31 vs 26.33 us, never enabled)
-    const dim3 grid(p.tiles_m * p.tiles_b * splitk);
+    if (w.exchange && !w.ticketed) p.fault = cdna4_gemm_fault_word();     // (the waiting hand-off)
+    p.tune = w.ticketed ? 2 : 0;      // bit1 = the ticketed split (gemm_w8_epilogue.inc); (bit0 = s_setprio 1 for the later-dispatched khalf-1 waves of k_gemm_kq_w8p: measured 26.31 vs 26.33 us, never enabled)
+    const dim3 grid(ntiles * w.splitk);
     // (the s_memtime trace instantiations <.., TRACE = true> exist in the -DCDNA4_ABLATIONS library of tools/microbench only)
 #ifdef CDNA4_ABLATIONS
 #define W8_LAUNCH(O) do { if (p.trace) hipLaunchKernelGGL((k_gemm_kq_w8<TYPE, true, O>), grid, dim3(512), 0, st, p); \
@@ -510,51 +534,57 @@ static int launch_w8(const cdna4_gemm_args &a, int splitk, int opt, hipStream_t 
 #else
 #define W8_LAUNCH(O) hipLaunchKernelGGL((k_gemm_kq_w8<TYPE, false, O>), grid, dim3(512), 0, st, p)
 #endif
-    {   // the cross-stage pipeline is written for K ranges of >= 3 superblocks per work-group; shallower ones take schedule 20
-        const int total = a.K / 256;
-        const int min_nsb = p.partial ? (p.sb_split < total - p.sb_split ? p.sb_split : total - p.sb_split) : total / splitk;
-        if ((opt == 64 || opt == 65) && min_nsb < 3) opt = 20;
-    }
-    // (what a type cannot reach is not instantiated: the re-laid formats (100..) never take the loader-wave kernel, the staged ones (200..) take nothing else — round 5: 9 kernels)
-    if constexpr (TYPE >= 100 && TYPE < 200) { if (opt == 65) return cdna4_set_error_msg("gemm_q: the re-laid formats run on k_gemm_kq_w8p / _w8"); }
-    else if (opt == 65) {                                                      // + loader waves
-        // experiment bits of k_gemm_kq_w12 (variant bits 16+), built in -DCDNA4_ABLATIONS libraries
-        // (tools/microbench) only: 1 = early table read (bit-identical, measured: no gain), 16.. = timing-only ablations
+    // (w8_make_plan refused what is not instantiated for TYPE)
+    if constexpr (TYPE < 100 || TYPE >= 200) if (w.opt == 65) {           // + loader waves
         if constexpr (TYPE == CDNA4_Q4_K) {
 #define W12_EXP(E) case E: hipLaunchKernelGGL((k_gemm_kq_w12<TYPE, true, E>), grid, dim3(768), 0, st, p); CDNA4_CHECK_LAUNCH(); return 0;
-            if (exp != 0) switch (exp) {
-#ifdef CDNA4_ABLATIONS
-                W12_EXP(1) W12_EXP(2) W12_EXP(4) W12_EXP(6) W12_EXP(16) W12_EXP(32) W12_EXP(64) W12_EXP(128) W12_EXP(256) W12_EXP(96) W12_EXP(224) W12_EXP(480) W12_EXP(288) W12_EXP(512) W12_EXP(544) W12_EXP(992)
-#endif
-                default: return cdna4_set_error_msg("gemm_q: this k_gemm_kq_w12 experiment is not built");
-            }
+            switch (w.exp) { W12_EXPS(W12_EXP) default: break; }
 #undef W12_EXP
         }
         hipLaunchKernelGGL((k_gemm_kq_w12<TYPE, true>), grid, dim3(768), 0, st, p);
         CDNA4_CHECK_LAUNCH(); return 0;
     }
-    if constexpr (TYPE >= 200) return cdna4_set_error_msg("gemm_q: staged formats run on the loader-wave kernel only");
-    else {
-    if (opt == 64) {                                                      // cross-stage pipeline
+    if constexpr (TYPE < 200) {
+        if (w.opt == 64) {                                                // cross-stage pipeline
 #ifdef CDNA4_ABLATIONS
-        if (p.trace) { hipLaunchKernelGGL((k_gemm_kq_w8p<TYPE, true>), grid, dim3(512), 0, st, p); CDNA4_CHECK_LAUNCH(); return 0; }
+            if (p.trace) { hipLaunchKernelGGL((k_gemm_kq_w8p<TYPE, true>), grid, dim3(512), 0, st, p); CDNA4_CHECK_LAUNCH(); return 0; }
 #endif
-        hipLaunchKernelGGL((k_gemm_kq_w8p<TYPE, false>), grid, dim3(512), 0, st, p);
-        CDNA4_CHECK_LAUNCH(); return 0;
-    }
-    else if constexpr (TYPE >= 100) { W8_LAUNCH(20); CDNA4_CHECK_LAUNCH(); return 0; }   // repacked formats: the default schedule only
-    else if ((opt & 31) == 20) W8_LAUNCH(20);                             // the in-wave pipeline with the DMA pieces split over both phases (shallow-K fallback)
-    else return cdna4_set_error_msg("gemm_q: of the 8-wave in-wave schedules only option 20 is built (variant 663)");
+            hipLaunchKernelGGL((k_gemm_kq_w8p<TYPE, false>), grid, dim3(512), 0, st, p);
+        } else W8_LAUNCH(20);                                             // the in-wave pipeline with the DMA pieces split over both phases (shallow-K fallback; repacked formats: their only other schedule)
 #undef W8_LAUNCH
+    }
     CDNA4_CHECK_LAUNCH();
     return 0;
-    }
 }
 
+static void plan_t64(gemm_q_plan &pl, const cdna4_gemm_args &k, int tm) {
+    pl.k = k; pl.terminal = GQ_T64; pl.kernel = 10; pl.tail_in_store = true;
+    pl.err = t64_make_plan(k, tm, k.splitk, pl.t64); pl.fuses_quantizer = pl.t64.fq;
+}
+static void plan_r8(gemm_q_plan &pl, const cdna4_gemm_args &k, int splitk) {
+    pl.k = k; pl.terminal = GQ_R8; pl.kernel = 12; pl.tail_in_store = true;
+    pl.err = r8_make_plan(k, splitk, pl.r8);
+}
+static void plan_w8(gemm_q_plan &pl, int type, const cdna4_gemm_args &k, int splitk, int opt, int exp = 0) {
+    pl.k = k; pl.terminal = GQ_W8; pl.kernel = 13;
+    pl.err = w8_make_plan(type, k, splitk, opt, exp, pl.w8); pl.tail_in_store = splitk == 1 || pl.w8.exchange;
+}
+// a resident kernel-native re-layout of the caller's rows (Q4_0R / Q8_0R / Q6_K8: cdna4_resident_*), 16-byte aligned: the arguments with it in W's place.  The image's
+// activations are not Q4_K's: such a launch never carries the quantizer (xf = nullptr)
+static bool resident_relayout(const cdna4_gemm_args &a, int image_type, int block_bytes, gemm_q_plan &pl, cdna4_gemm_args &r) {
+    const uint8_t *img = cdna4_resident_lookup(a.type, a.W, a.w_row_bytes, a.M, a.K);
+    if (!img || ((uintptr_t)img & 15)) return false;
+    r = a; r.type = image_type; r.W = img; r.w_row_bytes = (int64_t)(a.K / 256) * block_bytes; r.xf = nullptr;
+    pl.source = GQ_W_RESIDENT; pl.image = img;
+    return true;
+}
+
+// the plan of a call on one of the five formats with kernels of their own.  registered: a.W are the caller's rows (they may have a resident image); false: re-encoded
+// rows (a.W == nullptr: not there yet), which are 16-byte aligned and in no registry
 template <int TYPE>
-static int launch_type(const cdna4_gemm_args &a, hipStream_t st) {
+static void plan_type(const cdna4_gemm_args &a, bool registered, gemm_q_plan &pl) {
     constexpr bool CAN_LDS = QT<TYPE>::KQ && (QT<TYPE>::BYTES % 16 == 0);
-    // variant: bit0 = LDS weight staging (Q4_K/Q5_K only), bit1 = 128-wide activation tile, bit3 = the older
+    // variant (include/ggml_cdna4.h points here under this function's earlier name, launch_type()): bit0 = LDS weight staging (Q4_K/Q5_K only), bit1 = 128-wide activation tile, bit3 = the older
     // slice-per-barrier kernel instead of the pipelined one, bit4 = the 8-wave (two waves per SIMD) 128x128 kernel,
     // bits 5-9 = that kernel's schedule option OPT (see k_gemm_kq_w8; 20 = in-wave pipeline with the DMA pieces split over both phases),
     // bit11 = the cross-stage pipelined k_gemm_kq_w8p (the default),
@@ -579,108 +609,75 @@ static int launch_type(const cdna4_gemm_args &a, hipStream_t st) {
         if (variant & 16) splitk = (tiles * 2 <= cu_count() && kunits % 2 == 0 && kunits >= 4) ? 2 : 1;   // hand-off split: only if co-resident
         else splitk = 1;
         // An ODD number of superblocks — K = 11008 = 43 x 256, BASELINE configs[2] — also takes the hand-off split: its two
-        // work-groups get sb_split / total - sb_split superblocks (22 / 21), which the exchange was written for (launch_w8:
-        // p.sb_split).  Measured on MI355X (round-1 driver run): rel-L2 7.2e-7 vs the unsplit kernel, 59.7 vs 69.6 us.
+        // work-groups get sb_split / total - sb_split superblocks (22 / 21), which the exchange was written for (w8_make_plan:
+        // sb_split).  Measured on MI355X (round-1 driver run): rel-L2 7.2e-7 vs the unsplit kernel, 59.7 vs 69.6 us.
         if ((variant & 16) && wlds && QT<TYPE>::KQ && tiles * 2 <= cu_count() && (kunits & 1) && kunits >= 7) { splitk = 2; uneven = true; }
     }
     if constexpr (TYPE == CDNA4_Q4_K) {
         // bit13 = k_gemm_kq_t64 (gemm_q_t64.hip: 64(m) x 128(b) wave tiles); bit14 / bit15 force its 128- / 256-row tile
-        if (wlds && (variant & 8192)) { if (g_probe.active) g_probe.fuseq = cdna4_gemm_t64_fuses_quantizer(a, (variant & 16384) ? 128 : ((variant & 32768) ? 256 : 0), a.splitk); ROUTE_END_K(true, 10); return cdna4_launch_gemm_t64(a, (variant & 16384) ? 128 : ((variant & 32768) ? 256 : 0), a.splitk, st); }
+        if (wlds && (variant & 8192)) return plan_t64(pl, a, (variant & 16384) ? 128 : ((variant & 32768) ? 256 : 0));
         // auto (round 2): k_gemm_kq_t64 for every prefill shape — 128-row tiles (hand-off split-K = 2 while both work-groups of a tile
         // are resident, uneven for odd superblock counts), 256-row tiles once the grid holds two of them per CU.  MI355X, same box, same
         // data: 4096x4096x512 24.25 vs 24.68 us on k_gemm_kq_w12, 4096x11008x512 50.95 vs 52.57, 8192x4096x512 37.1 vs 38.1,
         // 32768x8192x512 (256-row tiles) 239-243 vs 265.
         // auto (round 4): k_gemm_r8 (gemm_r8.inc: 32 x 256 wave tiles, half the unpack VALU per MFMA) where its 256 x 256 tiles fill the chip unsplit — 9-10 % ahead there
-        if (wlds && a.variant <= 0 && a.splitk <= 0 && cdna4_gemm_r8_preferred(a)) { ROUTE_END_K(true, 12); return cdna4_launch_gemm_lds(a, 256, 1, st, 2); }
-        if (wlds && a.variant <= 0 && a.splitk <= 2) { if (g_probe.active) g_probe.fuseq = cdna4_gemm_t64_fuses_quantizer(a, 0, a.splitk); ROUTE_END_K(true, 10); return cdna4_launch_gemm_t64(a, 0, a.splitk, st); }   // (deeper, atomic splits: the older kernels below)
+        if (wlds && a.variant <= 0 && a.splitk <= 0 && cdna4_gemm_r8_preferred(a)) return plan_r8(pl, a, 1);
+        if (wlds && a.variant <= 0 && a.splitk <= 2) return plan_t64(pl, a, 0);      // (deeper, atomic splits: the older kernels below)
     }
     if constexpr (TYPE == CDNA4_Q5_K) {
         // round 4: k_gemm_r8 also unpacks Q5_K (its fifth bits cost 4-5 VALU per half2 pair: the format that gains most from one fragment meeting eight activation
         // fragments) — the same rule as Q4_K: grids of at least one 256 x 256 tile per CU, unsplit
-        if (wlds && a.variant <= 0 && a.splitk <= 0 && cdna4_gemm_r8_preferred(a)) { ROUTE_END_K(true, 12); return cdna4_launch_gemm_lds(a, 256, 1, st, 2); }
+        if (wlds && a.variant <= 0 && a.splitk <= 0 && cdna4_gemm_r8_preferred(a)) return plan_r8(pl, a, 1);
     }
-    if (splitk < 1 || (kunits % splitk && !uneven)) return cdna4_set_error_msg("gemm_q: splitk must divide the number of K units");
+    if (splitk < 1 || (kunits % splitk && !uneven)) { pl.err = "gemm_q: splitk must divide the number of K units"; return; }
+    [[maybe_unused]] cdna4_gemm_args r;                                   // the arguments with an image / the re-laid rows in W's place
     if constexpr (TYPE == CDNA4_Q4_0) {
         // round 5: a RESIDENT Q4_0R image of this matrix (cdna4_resident_*: built once by the host / the CDNA4_Resident buffer type) puts Q4_0 on Q4_K's own kernels —
         // k_gemm_r8 where its tiles fill the chip, k_gemm_kq_t64 otherwise (256-row tiles, ticketed / deep splits, the tail in the store) — instead of the staging kernel
-        if (a.variant <= 0 && a.splitk <= 2 && a.K % 256 == 0) {
-            const uint8_t *img = cdna4_resident_lookup(CDNA4_Q4_0, a.W, a.w_row_bytes, a.M, a.K);
-            if (img && !((uintptr_t)img & 15)) {
-                cdna4_gemm_args r = a; r.type = CDNA4_Q4_0R; r.W = img; r.w_row_bytes = (int64_t)(a.K / 256) * 144; r.xf = nullptr;
-                if (a.splitk <= 0 && cdna4_gemm_r8_preferred(r)) { ROUTE_END_K(true, 12); return cdna4_launch_gemm_lds(r, 256, 1, st, 2); }
-                ROUTE_END_K(true, 10);
-                return cdna4_launch_gemm_t64(r, 0, a.splitk, st);
-            }
-        }
+        if (registered && a.variant <= 0 && a.splitk <= 2 && a.K % 256 == 0 && resident_relayout(a, CDNA4_Q4_0R, 144, pl, r))
+            return (a.splitk <= 0 && cdna4_gemm_r8_preferred(r)) ? plan_r8(pl, r, 1) : plan_t64(pl, r, 0);
     }
     if constexpr (TYPE == CDNA4_Q8_0 || TYPE == CDNA4_Q6_K) {
         // round 5: a resident Q8_0R / Q6_K8 image puts Q8_0 / Q6_K on k_gemm_r8 where its 256 x 256 tiles fill the chip (k_gemm_r8<Q8_0R | Q6_K8>: 64 raw bytes per row and K tile)
-        if (a.variant <= 0 && a.splitk <= 0 && a.K % 256 == 0) {
-            const uint8_t *img = cdna4_resident_lookup(TYPE, a.W, a.w_row_bytes, a.M, a.K);
-            if (img && !((uintptr_t)img & 15)) {
-                cdna4_gemm_args r = a; r.type = TYPE == CDNA4_Q8_0 ? CDNA4_Q8_0R : CDNA4_Q6_K8; r.W = img; r.w_row_bytes = (int64_t)(a.K / 256) * (TYPE == CDNA4_Q8_0 ? 272 : 288); r.xf = nullptr;
-                if (cdna4_gemm_r8_preferred(r)) { ROUTE_END_K(true, 12); return cdna4_launch_gemm_lds(r, 256, 1, st, 2); }
-                // smaller grids.  For Q4_K k_gemm_r8's co-resident split-K (2 / 4 / 8 work-groups per tile reduce-scatter their partial tiles) is level with or behind
-                // k_gemm_kq_t64; Q8_0's alternative is the staging kernel, 35 % behind r8 per tile.  MI355X, one box, alternating, us per call, staging kernel -> r8
-                // (profiles/r05/q80_r8_small.txt):   split in 2 (65 .. 128 tiles): 16384 x 8192 x 512 178 -> 139, 14336 x 4096 x 512 91 -> 71, 4096 x 4096 x 2048 103 -> 79;
-                // split in 4 / 8 (<= 64 tiles): only long rows pay — 8192 x 8192 x 512 90.6 -> 83.7, 4096 x 14336 x 512 83.3 -> 77.3, but 8192 x 4096 x 512 48.7 -> 53.2,
-                // 4096 x 4096 x 1024 49.2 -> 52.7, 4096 x 4096 x 512 31.0 -> 40.2.  One ragged round of at least 65 % of the CUs runs unsplit.
-                const int nt256 = ((a.M + 255) / 256) * ((a.B + 255) / 256), cus = cu_count(), co = cdna4_gemm_coresident_cus();
-                if (nt256 < cus && nt256 * 20 >= cus * 13) { ROUTE_END_K(true, 12); return cdna4_launch_gemm_lds(r, 256, 1, st, 2); }
-                if (nt256 * 2 <= co && a.K >= 1024 && (nt256 * 4 > co || a.K >= 8192)) { ROUTE_END_K(true, 12); return cdna4_launch_gemm_lds(r, 256, 0, st, 2); }
-            }
+        if (registered && a.variant <= 0 && a.splitk <= 0 && a.K % 256 == 0 && resident_relayout(a, TYPE == CDNA4_Q8_0 ? CDNA4_Q8_0R : CDNA4_Q6_K8, TYPE == CDNA4_Q8_0 ? 272 : 288, pl, r)) {
+            if (cdna4_gemm_r8_preferred(r)) return plan_r8(pl, r, 1);
+            // smaller grids.  For Q4_K k_gemm_r8's co-resident split-K (2 / 4 / 8 work-groups per tile reduce-scatter their partial tiles) is level with or behind
+            // k_gemm_kq_t64; Q8_0's alternative is the staging kernel, 35 % behind r8 per tile.  MI355X, one box, alternating, us per call, staging kernel -> r8
+            // (profiles/r05/q80_r8_small.txt):   split in 2 (65 .. 128 tiles): 16384 x 8192 x 512 178 -> 139, 14336 x 4096 x 512 91 -> 71, 4096 x 4096 x 2048 103 -> 79;
+            // split in 4 / 8 (<= 64 tiles): only long rows pay — 8192 x 8192 x 512 90.6 -> 83.7, 4096 x 14336 x 512 83.3 -> 77.3, but 8192 x 4096 x 512 48.7 -> 53.2,
+            // 4096 x 4096 x 1024 49.2 -> 52.7, 4096 x 4096 x 512 31.0 -> 40.2.  One ragged round of at least 65 % of the CUs runs unsplit.
+            const int nt256 = ((a.M + 255) / 256) * ((a.B + 255) / 256), cus = cu_count(), co = cdna4_gemm_coresident_cus();
+            if (nt256 < cus && nt256 * 20 >= cus * 13) return plan_r8(pl, r, 1);
+            if (nt256 * 2 <= co && a.K >= 1024 && (nt256 * 4 > co || a.K >= 8192)) return plan_r8(pl, r, 0);
+            pl.source = GQ_W_GIVEN; pl.image = nullptr;                    // (the image goes unused: the routes below read the caller's rows)
         }
     }
     if constexpr (TYPE == CDNA4_Q4_0 || TYPE == CDNA4_Q8_0 || TYPE == CDNA4_Q6_K) {
-        // 2-byte-aligned formats at prefill batch sizes: re-lay the weights into 16-byte-aligned superblocks (scratch, per
-        // call: one extra read+write of W, ~5 us at 4096x4096) and run the LDS-DMA pipeline on that — 2.5-3x faster
-        // than the per-lane-load kernel below, which stays for small batches and K % 256 != 0.
+        // 2-byte-aligned formats at prefill batch sizes, K in whole superblocks.  Preferred: no copy at all — the loader waves of k_gemm_kq_w12 read the original blocks and
+        // re-lay them while staging (needs >= 3 superblocks of K per work-group, like the cross-stage pipeline itself).  Otherwise re-lay the weights into 16-byte-aligned
+        // superblocks (scratch kind 1, per call: one extra read+write of W, ~5 us at 4096x4096) and run the LDS-DMA pipeline on that — 2.5-3x faster than the per-lane-load
+        // kernel below, which stays for small batches and K % 256 != 0.
         constexpr int RT = TYPE == CDNA4_Q4_0 ? CDNA4_Q4_0R : (TYPE == CDNA4_Q8_0 ? CDNA4_Q8_0R : CDNA4_Q6_KR);
+        constexpr int ST_ = TYPE == CDNA4_Q4_0 ? CDNA4_Q4_0S : (TYPE == CDNA4_Q8_0 ? CDNA4_Q8_0S : CDNA4_Q6_KS);
         if (a.variant <= 0 && a.K % 256 == 0) {
-            // preferred: no copy at all — the loader waves of k_gemm_kq_w12 read the original blocks and re-lay them while
-            // staging (needs >= 3 superblocks of K per work-group, like the cross-stage pipeline itself)
-            constexpr int ST_ = TYPE == CDNA4_Q4_0 ? CDNA4_Q4_0S : (TYPE == CDNA4_Q8_0 ? CDNA4_Q8_0S : CDNA4_Q6_KS);
+            // the auto split of both routes: in two where both work-groups of every tile fit the chip and each gets at least two superblocks
             const int nsb = a.K / 256, tiles = ((a.M + 127) / 128) * ((a.B + 127) / 128);
-            int sk = a.splitk;
-            if (sk <= 0) sk = (tiles * 2 <= cu_count() && nsb % 2 == 0 && nsb >= 4) ? 2 : 1;
-            if (sk >= 1 && nsb % sk == 0 && nsb / sk >= 3) return launch_w8<ST_>(a, sk, 65, st);
-        }
-        if (a.variant <= 0 && a.K % 256 == 0) {
-            const int nsb = a.K / 256;
-            const size_t rbytes = (size_t)a.M * nsb * QT<RT>::BYTES;
-            if (g_probe.active) {                                        // (the same terminal, without the re-layout pass in front of it)
-                const int tiles = ((a.M + 127) / 128) * ((a.B + 127) / 128);
-                int sk = a.splitk;
-                if (sk <= 0) sk = (tiles * 2 <= cu_count() && nsb % 2 == 0 && nsb >= 4) ? 2 : 1;
-                if (sk < 1 || nsb % sk) return 0;
-                return launch_w8<RT>(a, sk, 64, st);
-            }
-            uint8_t *rw = (uint8_t *)get_scratch(rbytes + 256, 1);
-            if (!rw) return cdna4_set_error_msg("gemm_q: cannot allocate the repack scratch");
-            const dim3 grid((unsigned)(((int64_t)a.M * nsb * (QT<RT>::BYTES / 16) + 255) / 256));
-            if (TYPE == CDNA4_Q4_0) hipLaunchKernelGGL(k_repack_q4_0, grid, dim3(256), 0, st, a.W, a.w_row_bytes, a.M, nsb, rw);
-            else if (TYPE == CDNA4_Q8_0) hipLaunchKernelGGL(k_repack_q8_0, grid, dim3(256), 0, st, a.W, a.w_row_bytes, a.M, nsb, rw);
-            else hipLaunchKernelGGL(k_repack_q6_K, grid, dim3(256), 0, st, a.W, a.w_row_bytes, a.M, nsb, rw);
-            CDNA4_CHECK_LAUNCH();
-            cdna4_gemm_args r = a; r.W = rw; r.w_row_bytes = (int64_t)nsb * QT<RT>::BYTES;
-            const int tiles = ((a.M + 127) / 128) * ((a.B + 127) / 128);
-            int sk = a.splitk;
-            if (sk <= 0) sk = (tiles * 2 <= cu_count() && nsb % 2 == 0 && nsb >= 4) ? 2 : 1;
-            if (sk < 1 || nsb % sk) return cdna4_set_error_msg("gemm_q: splitk must divide the number of K units");
-            return launch_w8<RT>(r, sk, 64, st);
+            const int sk = a.splitk > 0 ? a.splitk : ((tiles * 2 <= cu_count() && nsb % 2 == 0 && nsb >= 4) ? 2 : 1);
+            if (nsb % sk == 0 && nsb / sk >= 3) return plan_w8(pl, ST_, a, sk, 65);
+            if (nsb % sk) { pl.err = "gemm_q: splitk must divide the number of K units"; return; }
+            r = a; r.W = nullptr; r.w_row_bytes = (int64_t)nsb * QT<RT>::BYTES;
+            pl.source = GQ_W_RELAID;
+            return plan_w8(pl, RT, r, sk, 64);
         }
     }
     if constexpr (CAN_LDS) {
-        if (wlds && (variant & 16)) return launch_w8<TYPE>(a, splitk, (variant & 4096) ? 65 : ((variant & 2048) ? 64 : ((variant >> 5) & 31)), st, variant >> 16);
+        if (wlds && (variant & 16)) return plan_w8(pl, TYPE, a, splitk, (variant & 4096) ? 65 : ((variant & 2048) ? 64 : ((variant >> 5) & 31)), variant >> 16);
     }
-    ROUTE_END_K(false, 14);                                              // the older kernels below store the plain product (k_epilogue behind them)
+    // the older kernel stores the plain product (k_epilogue behind it)
     // (round 5: the 4-wave pipelined k_gemm_kq_pipe and the 64-wide forms of k_gemm_q — explicit variants only since round 2 — are gone; bits 1 and 3 of a variant are ignored)
-    (void)wide;
-    if constexpr (CAN_LDS) {
-        if (wlds) return launch_variant<TYPE, 4, true>(a, splitk, st);
-    }
-    return launch_variant<TYPE, 4, false>(a, splitk, st);
+    pl.k = a; pl.terminal = GQ_KQ; pl.kernel = 14; pl.tail_in_store = false; pl.kq.wlds = wlds; pl.kq.splitk = splitk;
 }
+
 
 // grouped MUL_MAT_ID for Q5_K / Q6_K / Q4_0 / Q8_0: one launch of k_gemm_q<.., IDS> over (m tile) x (128-row activation tile of the expert-sorted
 // image); a.B = image rows (a multiple of 128), a.Y rows indexed through row_dst.  (Q4_K: cdna4_launch_gemm_t64_ids.)
@@ -712,68 +709,88 @@ int cdna4_launch_gemm_ids(const cdna4_gemm_args &a, const int32_t *tile_expert, 
     return cdna4_set_error_msg("gemm_ids: unsupported weight type");
 }
 
-int cdna4_launch_gemm_q(const cdna4_gemm_args &a, hipStream_t st);
-// does the route cdna4_launch_gemm_q() takes for these arguments apply a.epi in its store?  (k_gemm_kq_t64, k_gemm_r8 and the 128 x 128-tile kernels of
-// gemm_w8_epilogue.inc outside their atomic-sum split; also behind the exact re-encodings.)  Runs the routing itself with the probe armed: no side effects.
-bool cdna4_gemm_q_fuses_quantizer(const cdna4_gemm_args &a) {
-    g_probe.active = true; g_probe.fuses = false; g_probe.kernel = 0; g_probe.reencoded = 0; g_probe.fuseq = false;
-    const int rc = cdna4_launch_gemm_q(a, nullptr);
-    g_probe.active = false;
-    return rc == 0 && g_probe.fuseq;
-}
-bool cdna4_gemm_q_fuses_tail(const cdna4_gemm_args &a) {
-    g_probe.active = true; g_probe.fuses = false; g_probe.kernel = 0; g_probe.reencoded = 0; g_probe.fuseq = false;
-    const int rc = cdna4_launch_gemm_q(a, nullptr);
-    g_probe.active = false;
-    return rc == 0 && g_probe.fuses;
-}
-// which prefill kernel would cdna4_launch_gemm_q() launch for these arguments (ids above; + 100 behind an exact re-encoding; 0: none / error)?  No side effects.
-int cdna4_gemm_q_route(const cdna4_gemm_args &a) {
-    g_probe.active = true; g_probe.fuses = false; g_probe.kernel = 0; g_probe.reencoded = 0; g_probe.fuseq = false;
-    const int rc = cdna4_launch_gemm_q(a, nullptr);
-    g_probe.active = false;
-    if (rc == 0 && g_probe.kernel == 10 && g_probe.fuseq) return 11;                 // ONE launch: the activation quantizer inside k_gemm_kq_t64
-    return rc == 0 && g_probe.kernel ? g_probe.kernel + 100 * g_probe.reencoded : 0;
+// the terminals of this file for weights that are (or were re-encoded as) TYPE: the 128 x 128-tile kernels on TYPE itself, on its staged or on its re-laid form, or k_gemm_q
+template <int TYPE>
+static int launch_planned(const cdna4_gemm_args &k, const gemm_q_plan &pl, hipStream_t st) {
+    if (pl.terminal == GQ_W8) {
+        if constexpr (TYPE == CDNA4_Q4_0 || TYPE == CDNA4_Q8_0 || TYPE == CDNA4_Q6_K) {
+            constexpr int ST_ = TYPE == CDNA4_Q4_0 ? CDNA4_Q4_0S : (TYPE == CDNA4_Q8_0 ? CDNA4_Q8_0S : CDNA4_Q6_KS), RT = TYPE == CDNA4_Q4_0 ? CDNA4_Q4_0R : (TYPE == CDNA4_Q8_0 ? CDNA4_Q8_0R : CDNA4_Q6_KR);
+            return pl.w8.type == ST_ ? launch_w8<ST_>(k, pl.w8, st) : launch_w8<RT>(k, pl.w8, st);
+        } else return launch_w8<TYPE>(k, pl.w8, st);
+    }
+    if constexpr (QT<TYPE>::KQ && QT<TYPE>::BYTES % 16 == 0) { if (pl.kq.wlds) return launch_variant<TYPE, 4, true>(k, pl.kq.splitk, st); }
+    return launch_variant<TYPE, 4, false>(k, pl.kq.splitk, st);
 }
 
-int cdna4_launch_gemm_q(const cdna4_gemm_args &a, hipStream_t st) {
-    if (a.M <= 0 || a.B <= 0) return 0;
-    if (!cdna4_gemm_q_supported(a.type, a.M, a.K, a.B)) return cdna4_set_error_msg("gemm_q: unsupported type / shape");
-    if ((uintptr_t)a.xh & 15) return cdna4_set_error_msg("gemm_q: activation image must be 16-byte aligned");
-    if (((uintptr_t)a.W | (uintptr_t)a.w_row_bytes) & 1) return cdna4_set_error_msg("gemm_q: weight rows must be 2-byte aligned");
-    if ((a.type == CDNA4_Q4_K || a.type == CDNA4_Q5_K) && (((uintptr_t)a.W | (uintptr_t)a.w_row_bytes) & 15))
-        return cdna4_set_error_msg("gemm_q: Q4_K/Q5_K rows must be 16-byte aligned");
-    if (a.type == CDNA4_Q5_0 || a.type == CDNA4_Q3_K || a.type == CDNA4_Q2_K || a.type == CDNA4_Q4_1 || a.type == CDNA4_Q5_1 || a.type == CDNA4_IQ4_NL || a.type == CDNA4_IQ4_XS) {
-        // no MFMA kernel of their own: re-encode EXACTLY as Q8_0 / Q6_K into scratch (convert_w.hip) and run that format's GEMM
-        uint8_t *cw = (uint8_t *)(uintptr_t)256;                         // (route probe: an aligned stand-in, never dereferenced)
-        if (g_probe.active) g_probe.reencoded = 1;
-        if (!g_probe.active) {
-            const uint8_t *res = cdna4_resident_lookup(a.type, a.W, a.w_row_bytes, a.M, a.K);      // built once at load (CDNA4_Resident buffers): no conversion launch
-            if (res) cw = const_cast<uint8_t *>(res);
-            else {
-                cw = (uint8_t *)get_scratch(cdna4_convert_weights_bytes(a.type, a.M, a.K) + 256, 3);
-                if (!cw) return cdna4_set_error_msg("gemm_q: cannot allocate the weight re-encoding scratch");
-                const int rc = cdna4_launch_convert_weights(a.type, a.W, a.w_row_bytes, a.M, a.K, cw, st);
-                if (rc) return rc;
-            }
-        }
-        cdna4_gemm_args c = a; c.W = cw;
-        if (cdna4_convert_weights_target(a.type) == CDNA4_Q8_0) {
-            // Q5_0 / IQ4_NL: same shape.  Q4_1 / Q5_1: scale part and minimum part side by side, a.xh holds the activation image twice (capi.hip: prepare_act)
-            c.type = CDNA4_Q8_0; c.K = a.K * cdna4_convert_weights_kmul(a.type); c.xh_row_elems = c.K; c.w_row_bytes = (int64_t)(c.K / 32) * 34;
-            return launch_type<CDNA4_Q8_0>(c, st);
-        }
-        // Q3_K: same shape.  Q2_K (scale part | minimum part) and IQ4_XS (h part | l part): two column blocks, a.xh holds the activation image twice (capi.hip: prepare_act)
-        c.type = CDNA4_Q6_K; c.K = a.K * cdna4_convert_weights_kmul(a.type); c.xh_row_elems = c.K; c.w_row_bytes = (int64_t)(c.K / 256) * 210;
-        return launch_type<CDNA4_Q6_K>(c, st);
+static const char *plan_call(const cdna4_gemm_args &a, gemm_q_plan &pl) {
+    if (a.M <= 0 || a.B <= 0) return nullptr;                            // an empty product: nothing to launch
+    if (!cdna4_gemm_q_supported(a.type, a.M, a.K, a.B)) return "gemm_q: unsupported type / shape";
+    if ((uintptr_t)a.xh & 15) return "gemm_q: activation image must be 16-byte aligned";
+    if (((uintptr_t)a.W | (uintptr_t)a.w_row_bytes) & 1) return "gemm_q: weight rows must be 2-byte aligned";
+    if ((a.type == CDNA4_Q4_K || a.type == CDNA4_Q5_K) && (((uintptr_t)a.W | (uintptr_t)a.w_row_bytes) & 15)) return "gemm_q: Q4_K/Q5_K rows must be 16-byte aligned";
+    if (cdna4_convert_weights_target(a.type) >= 0) {
+        // no MFMA kernel of their own: re-encoded EXACTLY as Q8_0 / Q6_K (convert_w.hip) — a resident image built once at load (CDNA4_Resident buffers), or scratch per
+        // call — and that format's plan.  Q5_0 / IQ4_NL / Q3_K: same shape.  Q4_1 / Q5_1 (scale part and minimum part side by side), Q2_K (scale part | minimum part) and
+        // IQ4_XS (h part | l part): two column blocks, a.xh holds the activation image twice (capi.hip: prepare_act).  a.variant and a.splitk pass through to the target.
+        pl.reencoded = true; pl.mid_type = cdna4_convert_weights_target(a.type); pl.kmul = cdna4_convert_weights_kmul(a.type);
+        pl.image = cdna4_resident_lookup(a.type, a.W, a.w_row_bytes, a.M, a.K);
+        pl.source = pl.image ? GQ_W_RESIDENT : GQ_W_REENCODED;
+        cdna4_gemm_args c = a;
+        c.type = pl.mid_type; c.W = pl.image; c.K = a.K * pl.kmul; c.xh_row_elems = c.K;
+        pl.mid_row_bytes = c.w_row_bytes = c.type == CDNA4_Q8_0 ? (int64_t)(c.K / 32) * 34 : (int64_t)(c.K / 256) * 210;
+        if (c.type == CDNA4_Q8_0) plan_type<CDNA4_Q8_0>(c, false, pl); else plan_type<CDNA4_Q6_K>(c, false, pl);
+        return pl.err;
     }
     // variant bits 28 + 26 = k_gemm_r8 (gemm_q_lds.hip: in-register unpack, 32 x 256 wave tiles) explicitly (bits 16-24: ablation mask of -DCDNA4_ABLATIONS builds)
     if (a.variant > 0 && (a.variant & (1 << 28))) {
-        if (!(a.variant & (1 << 26))) return cdna4_set_error_msg("gemm_q: variant bit 28 without bit 26 named k_gemm_lds / k_gemm_w4, removed in round 5 (measured losses: profiles/r04/gemm_bench.txt)");
-        ROUTE_END_K(true, 12);
-        return cdna4_launch_gemm_lds(a, 256, a.splitk, st, 2);
+        if (!(a.variant & (1 << 26))) return "gemm_q: variant bit 28 without bit 26 named k_gemm_lds / k_gemm_w4, removed in round 5 (measured losses: profiles/r04/gemm_bench.txt)";
+        plan_r8(pl, a, a.splitk);
+        return pl.err;
     }
-    int rc = 0;
-    if (cdna4_dispatch(cdna4_main5{}, a.type, [&](auto t) { rc = launch_type<t.value>(a, st); })) return rc;
-    return cdna4_set_error_msg("gemm_q: unsupported weight type");
+    if (!cdna4_dispatch(cdna4_main5{}, a.type, [&](auto t) { plan_type<t.value>(a, true, pl); })) return "gemm_q: unsupported weight type";
+    return pl.err;
 }
+gemm_q_plan gemm_q_make_plan(const cdna4_gemm_args &a) {
+    gemm_q_plan pl{};
+    pl.source = GQ_W_GIVEN; pl.mid_type = a.type; pl.mid_row_bytes = a.w_row_bytes; pl.kmul = 1; pl.k = a;
+    pl.err = plan_call(a, pl);
+    if (pl.err) { pl.kernel = 0; pl.tail_in_store = pl.fuses_quantizer = false; }      // (a refused call: the queries answer "none")
+    return pl;
+}
+// the three questions about the route cdna4_launch_gemm_q() takes for these arguments, read from its plan: does the kernel apply a.epi in its store, does it quantize a.xf
+// itself, and which kernel is it (gemm_q_route_id: the ids above; + 100 behind an exact re-encoding; 11: k_gemm_kq_t64 with the quantizer inside; 0: none / refused)?
+bool cdna4_gemm_q_fuses_quantizer(const cdna4_gemm_args &a) { return gemm_q_make_plan(a).fuses_quantizer; }
+bool cdna4_gemm_q_fuses_tail(const cdna4_gemm_args &a) { return gemm_q_make_plan(a).tail_in_store; }
+int cdna4_gemm_q_route(const cdna4_gemm_args &a) { return gemm_q_route_id(gemm_q_make_plan(a)); }
+
+int cdna4_launch_gemm_q(const cdna4_gemm_args &a, hipStream_t st) {
+    const gemm_q_plan pl = gemm_q_make_plan(a);
+    if (pl.err) return cdna4_set_error_msg(pl.err);
+    if (pl.terminal == GQ_NONE) return 0;
+    const uint8_t *rows = pl.image ? pl.image : a.W;
+    if (pl.reencoded && !pl.image) {
+        uint8_t *cw = (uint8_t *)get_scratch(cdna4_convert_weights_bytes(a.type, a.M, a.K) + 256, 3);
+        if (!cw) return cdna4_set_error_msg("gemm_q: cannot allocate the weight re-encoding scratch");
+        if (const int rc = cdna4_launch_convert_weights(a.type, a.W, a.w_row_bytes, a.M, a.K, cw, st)) return rc;
+        rows = cw;
+    }
+    if (pl.source == GQ_W_RELAID) {                                      // rows of mid_type -> 16-byte-aligned superblocks
+        const int nsb = pl.k.K / 256;
+        uint8_t *rw = (uint8_t *)get_scratch((size_t)a.M * pl.k.w_row_bytes + 256, 1);
+        if (!rw) return cdna4_set_error_msg("gemm_q: cannot allocate the repack scratch");
+        const dim3 grid((unsigned)(((int64_t)a.M * (pl.k.w_row_bytes / 16) + 255) / 256));
+        if (pl.mid_type == CDNA4_Q4_0) hipLaunchKernelGGL(k_repack_q4_0, grid, dim3(256), 0, st, rows, pl.mid_row_bytes, a.M, nsb, rw);
+        else if (pl.mid_type == CDNA4_Q8_0) hipLaunchKernelGGL(k_repack_q8_0, grid, dim3(256), 0, st, rows, pl.mid_row_bytes, a.M, nsb, rw);
+        else hipLaunchKernelGGL(k_repack_q6_K, grid, dim3(256), 0, st, rows, pl.mid_row_bytes, a.M, nsb, rw);
+        CDNA4_CHECK_LAUNCH();
+        rows = rw;
+    }
+    cdna4_gemm_args k = pl.k; k.W = rows;
+    if (pl.terminal == GQ_T64) return cdna4_run_gemm_t64(k, pl.t64, st);
+    if (pl.terminal == GQ_R8) return cdna4_run_gemm_r8(k, pl.r8, st);
+    int rc = 0;
+    // (the five formats of cdna4_main5, in the order that keeps the kernels' order in the code object what it was before there was a plan)
+    cdna4_dispatch(cdna4_types<CDNA4_Q4_K, CDNA4_Q5_K, CDNA4_Q4_0, CDNA4_Q6_K, CDNA4_Q8_0>{}, pl.mid_type, [&](auto t) { rc = launch_planned<t.value>(k, pl, st); });
+    return rc;
+}
+

@@ -2,6 +2,8 @@
 // Replaces, for Q4_K at B > 8, what ggml_compute_forward_mul_mat does after the activations are quantized
 // (/root/reference/src/ggml-cpu/ggml-cpu.c:7510-7605).
 #include "gemm_q_common.h"
+#include "gemm_q_plan.hpp"
+#include "cdna4_formats.hpp"
 #include <stdlib.h>
 #include "gemm_q_hw.h"
 #include "gemm_kq_t64.inc"
@@ -27,26 +29,22 @@ static bool t64_fuses_quantizer(const cdna4_gemm_args &a, int nblk) {
     return units <= pass && units * 2 > pass;
 }
 
-// tile rows and split of the launch AUTO (or the given tm / splitk) takes: shared by the launcher and the route probe (`fq`: the quantizer rides inside)
-struct t64_plan { int tm, splitk, ntiles; bool ticketed2, fq; };
-static int t64_make_plan(const cdna4_gemm_args &a, int tm, int splitk, t64_plan &pl);
-
 bool cdna4_gemm_t64_fuses_quantizer(const cdna4_gemm_args &a, int tm, int splitk) {
     t64_plan pl;
-    return t64_make_plan(a, tm, splitk, pl) == 0 && pl.fq;
+    return !t64_make_plan(a, tm, splitk, pl) && pl.fq;
 }
 
-// tile rows (0 = choose) and split-K (0 = choose; 1 or 2) -> launch.  Returns 0, or a negative status with the error text set.
+// tile rows (0 = choose) and split-K (0 = choose; 1 or 2) -> plan, then launch.  Returns 0, or a negative status with the error text set.
 int cdna4_launch_gemm_t64(const cdna4_gemm_args &a, int tm, int splitk, hipStream_t st) {
     t64_plan pl;
-    const int prc = t64_make_plan(a, tm, splitk, pl);
-    if (prc) return prc;
-    tm = pl.tm; splitk = pl.splitk;
+    if (const char *err = t64_make_plan(a, tm, splitk, pl)) return cdna4_set_error_msg(err);
+    return cdna4_run_gemm_t64(a, pl, st);
+}
+
+int cdna4_run_gemm_t64(const cdna4_gemm_args &a, const t64_plan &pl, hipStream_t st) {
+    const int tm = pl.tm, splitk = pl.splitk, ntiles = pl.ntiles, nsb = a.K / 256;
     const bool ticketed2 = pl.ticketed2, fq = pl.fq;
-    const int cus = cdna4_gemm_cu_count(), nsb = a.K / 256;
-    const int tiles_b = (a.B + 127) / 128;
-    const int tiles_m = (a.M + tm - 1) / tm, ntiles = tiles_m * tiles_b;
-    (void)cus;
+    const int tiles_b = (a.B + 127) / 128, tiles_m = (a.M + tm - 1) / tm;
     gemm_params p{};
     p.W = a.W; p.w_row_bytes = a.w_row_bytes; p.xh = (const half_t *)a.xh; p.xh_row = a.xh_row_elems;
     p.Y = a.Y; p.y_row = a.y_row_elems; p.M = a.M; p.K = a.K; p.B = a.B; p.splitk = splitk;
@@ -56,9 +54,8 @@ int cdna4_launch_gemm_t64(const cdna4_gemm_args &a, int tm, int splitk, hipStrea
         // exchange slots: [tile][work-group of the tile][wave] x 16 KB at most; flag words: hand-off flags [tile][ks] in the first 32 KB,
         // deep-split ticket counters [tile] behind them, the grid barrier's words (FQ) at 48 KB; all zero when idle and reset by their last user — no per-launch state on the
         // host: graph-capturable.  Scratch kind 2: the older kernels' areas never mix with these.
-        // The words live at a FIXED place (the first 64 KB) so that no shape's exchange slots ever overlay another shape's flags.
+        // The words live at a FIXED place (the first 64 KB) so that no shape's exchange slots ever overlay another shape's flags (t64_make_plan bounds the tiles).
         const size_t pbytes = splitk >= 2 ? (size_t)ntiles * splitk * 8 * 16384 : 0, fbytes = 65536;
-        if ((size_t)ntiles * 8 > 32768) return cdna4_set_error_msg("gemm_t64: too many tiles for the split-K flag area");
         char *sc = (char *)cdna4_gemm_scratch(fbytes + pbytes, 2);
         if (!sc) return cdna4_set_error_msg("gemm_t64: cannot allocate split-K scratch");
         p.flags = (unsigned *)sc; p.gbar = (unsigned *)(sc + 49152);
@@ -87,32 +84,22 @@ int cdna4_launch_gemm_t64(const cdna4_gemm_args &a, int tm, int splitk, hipStrea
     if (fq && p.trace && !abl && p.epi.bias == nullptr && p.epi.act == 0 && p.epi.resid == nullptr) { hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_K, 128, false, 256, false, true>), grid, dim3(512), 0, st, p); CDNA4_CHECK_LAUNCH(); return 0; }
     if (abl) return cdna4_set_error_msg("gemm_t64: ablation not instantiated");
 #endif
+    // the instantiation: format (Q4_0R = a resident image of Q4_0: the same kernels, the {d, 0} sub-block constants) x quantizer inside (Q4_K on 128-row tiles only:
+    // t64_make_plan) x tail in the store x tile rows.  (The nesting and the lists' order keep the kernels' order in the code object what it was with an if-chain here.)
     const bool tail = p.epi.bias != nullptr || p.epi.act != 0 || p.epi.resid != nullptr;
-    if (a.type == CDNA4_Q4_0R) {                                         // (a resident Q4_0R image: the same kernels, the {d, 0} sub-block constants)
-        if (tail) {
-            if (tm == 128) hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_0R, 128, false, 0, true>), grid, dim3(512), 0, st, p);
-            else hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_0R, 256, false, 0, true>), grid, dim3(512), 0, st, p);
-        } else if (tm == 128) hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_0R, 128>), grid, dim3(512), 0, st, p);
-        else hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_0R, 256>), grid, dim3(512), 0, st, p);
-        CDNA4_CHECK_LAUNCH();
-        return 0;
-    }
-    if (fq) {                                                            // (128-row tiles only: t64_make_plan)
-        if (tail) hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_K, 128, false, 0, true, true>), grid, dim3(512), 0, st, p);
-        else hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_K, 128, false, 0, false, true>), grid, dim3(512), 0, st, p);
-    } else if (tail) {
-        if (tm == 128) hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_K, 128, false, 0, true>), grid, dim3(512), 0, st, p);
-        else hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_K, 256, false, 0, true>), grid, dim3(512), 0, st, p);
-    } else if (tm == 128) hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_K, 128>), grid, dim3(512), 0, st, p);
-    else hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_K, 256>), grid, dim3(512), 0, st, p);
+    cdna4_dispatch(cdna4_types<CDNA4_Q4_K, CDNA4_Q4_0R>{}, a.type, [&](auto T) { cdna4_dispatch(cdna4_types<0, 1>{}, (int)fq, [&](auto FQ) {
+        cdna4_dispatch(cdna4_types<0, 1>{}, (int)tail, [&](auto TAIL) { cdna4_dispatch(cdna4_types<256, 128>{}, tm, [&](auto TM) {
+            if constexpr (!FQ.value || (T.value == CDNA4_Q4_K && TM.value == 128))
+                hipLaunchKernelGGL((k_gemm_kq_t64<T.value, TM.value, false, 0, TAIL.value != 0, FQ.value != 0>), grid, dim3(512), 0, st, p); }); }); }); });
     CDNA4_CHECK_LAUNCH();
     return 0;
 }
 
-static int t64_make_plan(const cdna4_gemm_args &a, int tm, int splitk, t64_plan &pl) {
-    if (a.type != CDNA4_Q4_K && a.type != CDNA4_Q4_0R) return cdna4_set_error_msg("gemm_t64: Q4_K (or Q4_0 as its resident Q4_0R image) only");
-    if (a.K % 256 || a.K < 256) return cdna4_set_error_msg("gemm_t64: K must be a whole number of superblocks");
-    if ((((uintptr_t)a.W | (uintptr_t)a.w_row_bytes) & 15) || ((uintptr_t)a.xh & 15)) return cdna4_set_error_msg("gemm_t64: weight rows and the activation image must be 16-byte aligned");
+// tile rows and split of the launch AUTO (or the given tm / splitk) takes, and whether the quantizer rides inside (`fq`).  Side-effect free.
+const char *t64_make_plan(const cdna4_gemm_args &a, int tm, int splitk, t64_plan &pl) {
+    if (a.type != CDNA4_Q4_K && a.type != CDNA4_Q4_0R) return "gemm_t64: Q4_K (or Q4_0 as its resident Q4_0R image) only";
+    if (a.K % 256 || a.K < 256) return "gemm_t64: K must be a whole number of superblocks";
+    if ((((uintptr_t)a.W | (uintptr_t)a.w_row_bytes) & 15) || ((uintptr_t)a.xh & 15)) return "gemm_t64: weight rows and the activation image must be 16-byte aligned";
     const int cus = cdna4_gemm_cu_count(), nsb = a.K / 256;
     const int tiles_b = (a.B + 127) / 128;
     // 256-row tiles move half the activation bytes per MFMA and need no K reduction across four waves: they pay as soon as the grid holds ONE of them per CU.
@@ -128,7 +115,7 @@ static int t64_make_plan(const cdna4_gemm_args &a, int tm, int splitk, t64_plan 
         // (from 3/4 of a tile per CU: what was measured — 0.75 and above are wins, exactly 0.5 is a loss, the band between them was never run: ADVICE r4)
         tm = (t256 * 4 >= cus * 3 && eff(t256) * 1.10 >= eff(t128)) ? 256 : 128;
     }
-    if (tm != 128 && tm != 256) return cdna4_set_error_msg("gemm_t64: tile rows are 128 or 256");
+    if (tm != 128 && tm != 256) return "gemm_t64: tile rows are 128 or 256";
     const int tiles_m = (a.M + tm - 1) / tm, ntiles = tiles_m * tiles_b;
     // split-K: 2 = the hand-off between the two co-resident work-groups of a tile; 4 / 8 = deep split for grids far below the chip
     // (a few activation rows over a tall matrix), every work-group >= 2 superblocks, summed in fixed order by the last one to arrive
@@ -145,9 +132,9 @@ static int t64_make_plan(const cdna4_gemm_args &a, int tm, int splitk, t64_plan 
         if (tm == 128 && ntiles * 8 <= cus && nsb >= 16) splitk = 8;
     }
     if (splitk == 2 && tm == 128 && cdna4_gemm_shared_device()) ticketed2 = true;      // shared device: an EXPLICIT split in two takes the ticketed sum as well
-    if (splitk != 1 && splitk != 2 && splitk != 4 && splitk != 8) return cdna4_set_error_msg("gemm_t64: split-K is 1, 2, 4 or 8");
-    if (splitk == 2 && (ntiles * 2 > cus || nsb < 2)) return cdna4_set_error_msg("gemm_t64: the split-K hand-off needs every work-group resident and two superblocks");
-    if (splitk > 2 && (nsb < splitk || tm != 128)) return cdna4_set_error_msg("gemm_t64: the deep K split is built for 128-row tiles and needs a superblock per work-group");
+    if (splitk != 1 && splitk != 2 && splitk != 4 && splitk != 8) return "gemm_t64: split-K is 1, 2, 4 or 8";
+    if (splitk == 2 && (ntiles * 2 > cus || nsb < 2)) return "gemm_t64: the split-K hand-off needs every work-group resident and two superblocks";
+    if (splitk > 2 && (nsb < splitk || tm != 128)) return "gemm_t64: the deep K split is built for 128-row tiles and needs a superblock per work-group";
     // the split in two of a launch that carries the quantizer: its grid is resident by construction (t64_fuses_quantizer), so the hand-off — half tiles exchanged,
     // both work-groups store — is legitimate there and halves the parked bytes (the ticketed default parks whole tiles: WRITE_SIZE 25.2 MB for an 8.4 MB result,
     // profiles/r04/pmc_summary.txt).  CDNA4_FQ_TICKETED=1 keeps the ticketed sum (A/B).
@@ -157,7 +144,8 @@ static int t64_make_plan(const cdna4_gemm_args &a, int tm, int splitk, t64_plan 
     pl.fq = tm == 128 && t64_fuses_quantizer(a, ntiles * splitk);
     static const bool fq_ticketed = getenv("CDNA4_FQ_TICKETED") && atoi(getenv("CDNA4_FQ_TICKETED")) != 0;
     if (pl.fq && splitk == 2 && tm == 128 && !fq_ticketed) pl.ticketed2 = false;
-    return 0;
+    if ((splitk >= 2 || pl.fq) && (size_t)ntiles * 8 > 32768) return "gemm_t64: too many tiles for the split-K flag area";
+    return nullptr;
 }
 
 // grouped MUL_MAT_ID: one launch over (m tile) x (activation tile of the expert-sorted image); tiles past the last expert's run exit

@@ -76,8 +76,8 @@ def test_workspace_size_is_monotonic_and_aligned(built):
 
 
 def test_tail_predictor_is_the_routing_itself_and_needs_no_device(built):
-    """ggml_cdna4_mul_mat_fused_residual_may_alias asks the ROUTING (gemm_q_mfma.hip: cdna4_gemm_q_fuses_tail runs cdna4_launch_gemm_q with a probe armed — no scratch, no
-    launch) whether the kernel AUTO would take applies the tail in its store; host logic, callable without a GPU.  Pinned here: every route that stores whole finished tiles says
+    """ggml_cdna4_mul_mat_fused_residual_may_alias asks the ROUTING (gemm_q_mfma.hip: gemm_q_make_plan, the side-effect-free plan cdna4_launch_gemm_q itself executes — no
+    scratch, no launch) whether the kernel AUTO would take applies the tail in its store; host logic, callable without a GPU.  Pinned here: every route that stores whole finished tiles says
     1 — the GEMV / int8 matrix-core family at small batches, k_gemm_kq_t64 / k_gemm_r8 (Q4_K, Q5_K), the 128 x 128-tile kernels of Q5_K / Q6_K / Q4_0 / Q8_0, and the GEMMs behind the
     exact re-encodings (Q5_0, Q2_K, IQ4_NL, IQ4_XS ...) — and the older per-lane-load kernels (32-weight formats with K not a multiple of 256) say 0: there the call with an aliased
     residual is refused instead of computing 2 (W x) + b."""

@@ -630,6 +630,136 @@ def test_flash_attn_refuses_invalid_calls_before_any_launch():
     assert got == [(-1, m) for _, m in FATTN_REJECTED], [(c, g, m) for (c, m), g in zip(FATTN_REJECTED, got) if g != (-1, m)]
 
 
+# Prefill GEMM routing plans (gemm_q_plan.hpp's gemm_q_make_plan through `lib_emul plan`).  Call: "type M K B splitk variant w_offset xf image" (type: the ggml type id; w_offset: of
+# the weights from a 4096-byte boundary; xf: the fp32 rows are handed over; image: a resident image is registered), under a CU count and routing knobs.  The expected values are what the
+# launcher did BEFORE it had a plan: recorded from the launches of the probe-era library (kernel instantiation, grid, gemm_params, where W points, the zero-fill / conversion / re-layout
+# launches in front, k_epilogue behind) with the launch calls replaced by prints — not taken from gemm_q_make_plan.  (tail of a call with an explicit split or variant, which the
+# fused entry point cannot name: the kernels' own rule — k_gemm_q and the atomic-sum split store the plain product.)
+GEMM_PLAN_TABLE = [
+    (256, {}, "12 4096 4096 1024 0 0 0 1 0", "ok=1 kernel=10 route=10 reenc=0 tail=1 fq=0 src=given wtype=12 wrow=2304 kmul=1 term=t64 tm=128 splitk=1 ntiles=256 ticketed=0 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {}, "12 4096 4096 512 0 0 0 1 0", "ok=1 kernel=10 route=10 reenc=0 tail=1 fq=0 src=given wtype=12 wrow=2304 kmul=1 term=t64 tm=128 splitk=2 ntiles=128 ticketed=1 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {}, "12 256 512 64 0 0 0 1 0", "ok=1 kernel=10 route=10 reenc=0 tail=1 fq=0 src=given wtype=12 wrow=288 kmul=1 term=t64 tm=128 splitk=2 ntiles=2 ticketed=1 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {}, "12 4096 2048 128 0 0 0 1 0", "ok=1 kernel=10 route=10 reenc=0 tail=1 fq=0 src=given wtype=12 wrow=1152 kmul=1 term=t64 tm=128 splitk=4 ntiles=32 ticketed=1 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {}, "12 128 4096 16 0 0 0 1 0", "ok=1 kernel=10 route=10 reenc=0 tail=1 fq=0 src=given wtype=12 wrow=2304 kmul=1 term=t64 tm=128 splitk=8 ntiles=1 ticketed=1 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {}, "12 16384 4096 512 0 0 0 1 0", "ok=1 kernel=10 route=10 reenc=0 tail=1 fq=0 src=given wtype=12 wrow=2304 kmul=1 term=t64 tm=256 splitk=1 ntiles=256 ticketed=0 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {"GGML_CDNA4_OWNED_DEVICE": "1", "CDNA4_T64_HANDOFF": "1"}, "12 4096 4096 512 0 0 0 1 0", "ok=1 kernel=10 route=11 reenc=0 tail=1 fq=1 src=given wtype=12 wrow=2304 kmul=1 term=t64 tm=128 splitk=2 ntiles=128 ticketed=0 waits=1 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {"GGML_CDNA4_OWNED_DEVICE": "1"}, "12 4096 4096 512 0 0 0 1 0", "ok=1 kernel=10 route=11 reenc=0 tail=1 fq=1 src=given wtype=12 wrow=2304 kmul=1 term=t64 tm=128 splitk=2 ntiles=128 ticketed=0 waits=1 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {}, "12 4096 4096 512 2 0 0 1 0", "ok=1 kernel=10 route=10 reenc=0 tail=1 fq=0 src=given wtype=12 wrow=2304 kmul=1 term=t64 tm=128 splitk=2 ntiles=128 ticketed=1 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {}, "12 4096 4096 512 0 24576 0 1 0", "ok=1 kernel=14 route=14 reenc=0 tail=0 fq=0 src=given wtype=12 wrow=2304 kmul=1 term=kq tm=128 splitk=1 ntiles=128 ticketed=0 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {}, "12 4096 512 4096 0 0 0 1 0", "ok=1 kernel=12 route=12 reenc=0 tail=1 fq=0 src=given wtype=12 wrow=288 kmul=1 term=r8 tm=256 splitk=1 ntiles=256 ticketed=0 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {}, "13 4096 512 4096 0 0 0 1 0", "ok=1 kernel=12 route=12 reenc=0 tail=1 fq=0 src=given wtype=13 wrow=352 kmul=1 term=r8 tm=256 splitk=1 ntiles=256 ticketed=0 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {}, "8 4096 1024 2816 0 0 0 1 1", "ok=1 kernel=12 route=12 reenc=0 tail=1 fq=0 src=resident wtype=108 wrow=1088 kmul=1 term=r8 tm=256 splitk=1 ntiles=176 ticketed=0 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {"GGML_CDNA4_OWNED_DEVICE": "1"}, "14 4096 1024 2048 0 0 0 1 1", "ok=1 kernel=12 route=12 reenc=0 tail=1 fq=0 src=resident wtype=115 wrow=1152 kmul=1 term=r8 tm=256 splitk=2 ntiles=128 ticketed=0 waits=1 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {"GGML_CDNA4_OWNED_DEVICE": "1"}, "8 4096 8192 512 0 0 0 1 1", "ok=1 kernel=12 route=12 reenc=0 tail=1 fq=0 src=resident wtype=108 wrow=8704 kmul=1 term=r8 tm=256 splitk=8 ntiles=32 ticketed=0 waits=1 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {}, "2 4096 4096 512 0 0 0 1 1", "ok=1 kernel=10 route=10 reenc=0 tail=1 fq=0 src=resident wtype=102 wrow=2304 kmul=1 term=t64 tm=128 splitk=2 ntiles=128 ticketed=1 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {}, "2 4096 512 4096 0 0 0 1 1", "ok=1 kernel=12 route=12 reenc=0 tail=1 fq=0 src=resident wtype=102 wrow=288 kmul=1 term=r8 tm=256 splitk=1 ntiles=256 ticketed=0 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {}, "12 4096 4096 512 0 335544320 0 1 0", "ok=1 kernel=12 route=12 reenc=0 tail=1 fq=0 src=given wtype=12 wrow=2304 kmul=1 term=r8 tm=256 splitk=1 ntiles=32 ticketed=0 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {}, "8 4096 4096 512 0 0 0 1 0", "ok=1 kernel=13 route=13 reenc=0 tail=1 fq=0 src=given wtype=208 wrow=4352 kmul=1 term=w8 tm=128 splitk=2 ntiles=128 ticketed=1 waits=0 zero=0 opt=65 sb_split=8 xchg_l2=1"),
+    (256, {}, "8 256 768 64 0 0 0 1 0", "ok=1 kernel=13 route=13 reenc=0 tail=1 fq=0 src=given wtype=208 wrow=816 kmul=1 term=w8 tm=128 splitk=1 ntiles=2 ticketed=0 waits=0 zero=0 opt=65 sb_split=0 xchg_l2=0"),
+    (256, {}, "14 4096 11008 512 0 0 0 1 0", "ok=1 kernel=13 route=13 reenc=0 tail=1 fq=0 src=given wtype=214 wrow=9030 kmul=1 term=w8 tm=128 splitk=1 ntiles=128 ticketed=0 waits=0 zero=0 opt=65 sb_split=0 xchg_l2=0"),
+    (256, {}, "8 256 256 64 0 0 0 1 0", "ok=1 kernel=13 route=13 reenc=0 tail=1 fq=0 src=relaid wtype=108 wrow=272 kmul=1 term=w8 tm=128 splitk=1 ntiles=2 ticketed=0 waits=0 zero=0 opt=20 sb_split=0 xchg_l2=0"),
+    (256, {}, "14 256 512 64 0 0 0 1 0", "ok=1 kernel=13 route=13 reenc=0 tail=1 fq=0 src=relaid wtype=114 wrow=448 kmul=1 term=w8 tm=128 splitk=1 ntiles=2 ticketed=0 waits=0 zero=0 opt=20 sb_split=0 xchg_l2=0"),
+    (256, {}, "2 256 512 64 0 0 0 1 0", "ok=1 kernel=13 route=13 reenc=0 tail=1 fq=0 src=relaid wtype=102 wrow=288 kmul=1 term=w8 tm=128 splitk=1 ntiles=2 ticketed=0 waits=0 zero=0 opt=20 sb_split=0 xchg_l2=0"),
+    (256, {}, "8 4096 1024 512 0 0 0 1 0", "ok=1 kernel=13 route=13 reenc=0 tail=1 fq=0 src=relaid wtype=108 wrow=1088 kmul=1 term=w8 tm=128 splitk=2 ntiles=128 ticketed=1 waits=0 zero=0 opt=20 sb_split=2 xchg_l2=1"),
+    (256, {}, "13 4096 4096 512 0 0 0 1 0", "ok=1 kernel=13 route=13 reenc=0 tail=1 fq=0 src=given wtype=13 wrow=2816 kmul=1 term=w8 tm=128 splitk=2 ntiles=128 ticketed=1 waits=0 zero=0 opt=64 sb_split=8 xchg_l2=1"),
+    (256, {}, "13 256 1024 64 0 0 0 1 0", "ok=1 kernel=13 route=13 reenc=0 tail=1 fq=0 src=given wtype=13 wrow=704 kmul=1 term=w8 tm=128 splitk=2 ntiles=2 ticketed=1 waits=0 zero=0 opt=20 sb_split=2 xchg_l2=0"),
+    (256, {}, "13 4096 11008 512 0 0 0 1 0", "ok=1 kernel=13 route=13 reenc=0 tail=1 fq=0 src=given wtype=13 wrow=7568 kmul=1 term=w8 tm=128 splitk=2 ntiles=128 ticketed=1 waits=0 zero=0 opt=64 sb_split=22 xchg_l2=1"),
+    (256, {"GGML_CDNA4_OWNED_DEVICE": "1"}, "13 4096 4096 512 2 0 0 1 0", "ok=1 kernel=13 route=13 reenc=0 tail=1 fq=0 src=given wtype=13 wrow=2816 kmul=1 term=w8 tm=128 splitk=2 ntiles=128 ticketed=0 waits=1 zero=0 opt=64 sb_split=8 xchg_l2=1"),
+    (256, {}, "12 4096 4096 512 0 4119 0 1 0", "ok=1 kernel=13 route=13 reenc=0 tail=1 fq=0 src=given wtype=12 wrow=2304 kmul=1 term=w8 tm=128 splitk=2 ntiles=128 ticketed=1 waits=0 zero=0 opt=65 sb_split=8 xchg_l2=1"),
+    (256, {}, "12 4096 4096 512 4 0 0 1 0", "ok=1 kernel=13 route=13 reenc=0 tail=0 fq=0 src=given wtype=12 wrow=2304 kmul=1 term=w8 tm=128 splitk=4 ntiles=128 ticketed=0 waits=0 zero=1 opt=65 sb_split=0 xchg_l2=0"),
+    (256, {}, "13 256 1024 64 4 0 0 1 0", "ok=1 kernel=13 route=13 reenc=0 tail=0 fq=0 src=given wtype=13 wrow=704 kmul=1 term=w8 tm=128 splitk=4 ntiles=2 ticketed=0 waits=0 zero=1 opt=20 sb_split=0 xchg_l2=0"),
+    (256, {}, "13 4096 4096 512 0 663 0 1 0", "ok=1 kernel=13 route=13 reenc=0 tail=1 fq=0 src=given wtype=13 wrow=2816 kmul=1 term=w8 tm=128 splitk=2 ntiles=128 ticketed=1 waits=0 zero=0 opt=20 sb_split=8 xchg_l2=1"),
+    (256, {}, "8 4096 4032 512 0 0 0 1 0", "ok=1 kernel=14 route=14 reenc=0 tail=0 fq=0 src=given wtype=8 wrow=4284 kmul=1 term=kq tm=128 splitk=1 ntiles=128 ticketed=0 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {}, "8 256 320 64 0 0 0 1 0", "ok=1 kernel=14 route=14 reenc=0 tail=0 fq=0 src=given wtype=8 wrow=340 kmul=1 term=kq tm=128 splitk=1 ntiles=2 ticketed=0 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {}, "8 4096 4032 512 3 0 0 1 0", "ok=1 kernel=14 route=14 reenc=0 tail=0 fq=0 src=given wtype=8 wrow=4284 kmul=1 term=kq tm=128 splitk=3 ntiles=128 ticketed=0 waits=0 zero=1 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {}, "6 256 768 64 0 0 0 1 0", "ok=1 kernel=13 route=113 reenc=1 tail=1 fq=0 src=reencoded wtype=208 wrow=816 kmul=1 term=w8 tm=128 splitk=1 ntiles=2 ticketed=0 waits=0 zero=0 opt=65 sb_split=0 xchg_l2=0"),
+    (256, {}, "20 4096 4096 512 0 0 0 1 0", "ok=1 kernel=13 route=113 reenc=1 tail=1 fq=0 src=reencoded wtype=208 wrow=4352 kmul=1 term=w8 tm=128 splitk=2 ntiles=128 ticketed=1 waits=0 zero=0 opt=65 sb_split=8 xchg_l2=1"),
+    (256, {}, "11 256 768 64 0 0 0 1 0", "ok=1 kernel=13 route=113 reenc=1 tail=1 fq=0 src=reencoded wtype=214 wrow=630 kmul=1 term=w8 tm=128 splitk=1 ntiles=2 ticketed=0 waits=0 zero=0 opt=65 sb_split=0 xchg_l2=0"),
+    (256, {}, "3 256 256 64 0 0 0 1 0", "ok=1 kernel=13 route=113 reenc=1 tail=1 fq=0 src=relaid wtype=108 wrow=544 kmul=2 term=w8 tm=128 splitk=1 ntiles=2 ticketed=0 waits=0 zero=0 opt=20 sb_split=0 xchg_l2=0"),
+    (256, {}, "7 4096 4096 512 0 0 0 1 0", "ok=1 kernel=13 route=113 reenc=1 tail=1 fq=0 src=reencoded wtype=208 wrow=8704 kmul=2 term=w8 tm=128 splitk=2 ntiles=128 ticketed=1 waits=0 zero=0 opt=65 sb_split=16 xchg_l2=1"),
+    (256, {}, "10 256 768 64 0 0 0 1 0", "ok=1 kernel=13 route=113 reenc=1 tail=1 fq=0 src=reencoded wtype=214 wrow=1260 kmul=2 term=w8 tm=128 splitk=2 ntiles=2 ticketed=1 waits=0 zero=0 opt=65 sb_split=3 xchg_l2=0"),
+    (256, {}, "23 256 512 64 0 0 0 1 0", "ok=1 kernel=13 route=113 reenc=1 tail=1 fq=0 src=relaid wtype=114 wrow=896 kmul=2 term=w8 tm=128 splitk=2 ntiles=2 ticketed=1 waits=0 zero=0 opt=20 sb_split=2 xchg_l2=0"),
+    (256, {}, "6 4096 4096 512 0 0 0 1 1", "ok=1 kernel=13 route=113 reenc=1 tail=1 fq=0 src=resident wtype=208 wrow=4352 kmul=1 term=w8 tm=128 splitk=2 ntiles=128 ticketed=1 waits=0 zero=0 opt=65 sb_split=8 xchg_l2=1"),
+    (256, {}, "6 256 320 64 0 0 0 1 0", "ok=1 kernel=14 route=114 reenc=1 tail=0 fq=0 src=reencoded wtype=8 wrow=340 kmul=1 term=kq tm=128 splitk=1 ntiles=2 ticketed=0 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (8, {}, "12 256 512 64 0 0 0 1 0", "ok=1 kernel=10 route=10 reenc=0 tail=1 fq=0 src=given wtype=12 wrow=288 kmul=1 term=t64 tm=128 splitk=2 ntiles=2 ticketed=1 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (8, {}, "12 4096 4096 512 0 0 0 1 0", "ok=1 kernel=12 route=12 reenc=0 tail=1 fq=0 src=given wtype=12 wrow=2304 kmul=1 term=r8 tm=256 splitk=1 ntiles=32 ticketed=0 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (8, {}, "12 4096 1024 100 0 0 0 1 0", "ok=1 kernel=12 route=12 reenc=0 tail=1 fq=0 src=given wtype=12 wrow=576 kmul=1 term=r8 tm=256 splitk=1 ntiles=16 ticketed=0 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (8, {}, "8 4096 4096 512 0 0 0 1 0", "ok=1 kernel=13 route=13 reenc=0 tail=1 fq=0 src=given wtype=208 wrow=4352 kmul=1 term=w8 tm=128 splitk=1 ntiles=128 ticketed=0 waits=0 zero=0 opt=65 sb_split=0 xchg_l2=0"),
+    (8, {}, "13 4096 4096 512 0 0 0 1 0", "ok=1 kernel=12 route=12 reenc=0 tail=1 fq=0 src=given wtype=13 wrow=2816 kmul=1 term=r8 tm=256 splitk=1 ntiles=32 ticketed=0 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (8, {"GGML_CDNA4_OWNED_DEVICE": "1"}, "8 256 4096 256 0 0 0 1 1", "ok=1 kernel=13 route=13 reenc=0 tail=1 fq=0 src=given wtype=208 wrow=4352 kmul=1 term=w8 tm=128 splitk=2 ntiles=4 ticketed=1 waits=0 zero=0 opt=65 sb_split=8 xchg_l2=0"),
+    (256, {}, "12 4096 4096 512 0 24577 0 1 0", "ok=1 kernel=10 route=10 reenc=0 tail=1 fq=0 src=given wtype=12 wrow=2304 kmul=1 term=t64 tm=128 splitk=2 ntiles=128 ticketed=1 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {}, "12 4096 4096 512 0 40961 0 1 0", "ok=1 kernel=10 route=10 reenc=0 tail=1 fq=0 src=given wtype=12 wrow=2304 kmul=1 term=t64 tm=256 splitk=1 ntiles=64 ticketed=0 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {"CDNA4_NO_R8": "1"}, "12 4096 512 4096 0 0 0 1 0", "ok=1 kernel=10 route=10 reenc=0 tail=1 fq=0 src=given wtype=12 wrow=288 kmul=1 term=t64 tm=256 splitk=1 ntiles=512 ticketed=0 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {"GGML_CDNA4_OWNED_DEVICE": "1", "CDNA4_NO_FUSEQ": "1"}, "12 4096 4096 512 0 0 0 1 0", "ok=1 kernel=10 route=10 reenc=0 tail=1 fq=0 src=given wtype=12 wrow=2304 kmul=1 term=t64 tm=128 splitk=2 ntiles=128 ticketed=1 waits=0 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {"GGML_CDNA4_OWNED_DEVICE": "1", "CDNA4_FQ_TICKETED": "1"}, "12 4096 4096 512 0 0 0 1 0", "ok=1 kernel=10 route=11 reenc=0 tail=1 fq=1 src=given wtype=12 wrow=2304 kmul=1 term=t64 tm=128 splitk=2 ntiles=128 ticketed=1 waits=1 zero=0 opt=0 sb_split=0 xchg_l2=0"),
+    (256, {"CDNA4_W8_HANDOFF": "1", "GGML_CDNA4_OWNED_DEVICE": "1"}, "13 4096 4096 512 0 0 0 1 0", "ok=1 kernel=13 route=13 reenc=0 tail=1 fq=0 src=given wtype=13 wrow=2816 kmul=1 term=w8 tm=128 splitk=2 ntiles=128 ticketed=0 waits=1 zero=0 opt=64 sb_split=8 xchg_l2=1"),
+]
+
+
+def _gemm_plans_by_setting(rows):
+    """rows (cus, env, call, ..) -> their plans, one `lib_emul plan` process per (cus, env)"""
+    mod, out, groups = _emul_module("lib_emul_check"), {}, {}
+    for i, r in enumerate(rows):
+        groups.setdefault((r[0], tuple(sorted(r[1].items()))), []).append(i)
+    for (cus, env), idx in groups.items():
+        for i, p in zip(idx, mod.plan([rows[i][2].split() for i in idx], cus=cus, env=dict(env))):
+            out[i] = p
+    return [out[i] for i in range(len(rows))]
+
+
+def test_prefill_gemm_routing_plans_of_a_table_of_shapes():
+    """every routing rule of the prefill GEMM at a shape that takes it, with the plan the call must get (see GEMM_PLAN_TABLE): kernel and route id, re-encoding, tail and quantizer
+    in the launch, where the weights come from and in which format, the terminal's tiles, split, exchange and schedule.  And the call on the same arguments executes it (rc 0)."""
+    for (cus, env, call, want), p in zip(GEMM_PLAN_TABLE, _gemm_plans_by_setting(GEMM_PLAN_TABLE)):
+        assert p["line"] == want and p["pure"] == 1 and p["rc"] == 0, (cus, env, call, p["line"], p["msg"])
+
+
+@pytest.mark.parametrize("cus,env", [(256, {}), (256, {"GGML_CDNA4_OWNED_DEVICE": "1"}), (8, {}), (8, {"GGML_CDNA4_OWNED_DEVICE": "1"})])
+def test_prefill_gemm_routing_plan_properties(cus, env):
+    """what holds for the plan of ANY call, over some ten thousand (type, M, K, B, splitk, variant, alignment, image) cells in the shared and the owned mode: the plan refuses exactly
+    the calls cdna4_launch_gemm_q refuses, with its message; the tail is outside the store exactly on k_gemm_q and on the atomic-sum split of the 128 x 128-tile kernels; the quantizer
+    rides only in k_gemm_kq_t64 on Q4_K's 128-row tiles of a device the caller owns; AUTO never waits for a co-resident work-group on a shared device; planning is repeatable
+    and leaves the error text alone"""
+    r8 = (1 << 28) | (1 << 26)
+    knobs = [(0, 0), (1, 0), (2, 0), (3, 0), (4, 0), (8, 0), (0, 8193), (0, 24577), (0, 40961), (2, 8193), (0, 1 << 28), (0, r8), (2, r8), (0, 23 | 2048), (0, 23 | 4096), (0, 23 | (20 << 5)),
+             (0, 23), (0, 4), (4, 23 | 2048), (0, 8192)]
+    cells = [(t, m, k, b, sk, v, off, 1, img) for _, t in LIB_TYPES for m in (130, 256, 4096) for k in (256, 768, 1024, 4032, 4096, 11008) for b in (9, 65, 128, 512, 2048)
+             for sk, v in knobs for off, img in ((0, 0), (2, 0), (0, 1)) if (off == 0 and img == 0) or (sk, v) == (0, 0)]
+    cells += [(12, 0, 256, 64, 0, 0, 0, 1, 0), (12, 256, 256, 0, 0, 0, 0, 1, 0), (12, 32768, 8192, 512, 0, 0, 0, 1, 0), (8, 16384, 8192, 512, 0, 0, 0, 1, 1), (8, 8192, 8192, 512, 0, 0, 0, 1, 1)]
+    assert len(cells) > 20000
+    owned = bool(env)
+    seen = set()
+    for c, p in zip(cells, _emul_module("lib_emul_check").plan(cells, cus=cus, env=env)):
+        why = (c, p["line"], p["rc"], p["msg"])
+        assert p["pure"] == 1, why
+        assert (p["ok"] == 1) == (p["rc"] == 0), why
+        if not p["ok"]:
+            assert p["rc"] == -1 and p["plan_err"] == 1 and (p["kernel"], p["route"], p["tail"], p["fq"]) == (0, 0, 0, 0), why
+            continue
+        if p["term"] == "none":
+            assert c[1] <= 0 or c[3] <= 0, why
+            continue
+        seen.add((p["term"], p["src"], p["fq"], p["waits"], p["reenc"]))
+        assert p["kernel"] == {"t64": 10, "r8": 12, "w8": 13, "kq": 14}[p["term"]] and p["route"] == (11 if p["fq"] else p["kernel"] + 100 * p["reenc"]), why
+        assert (p["tail"] == 0) == (p["kernel"] == 14 or (p["kernel"] == 13 and p["zero"] == 1)), why
+        if p["fq"]:
+            assert owned and p["kernel"] == 10 and p["wtype"] == 12 and c[0] == 12 and p["tm"] == 128 and p["waits"] == 1, why
+        if not owned:                                                    # AUTO, and explicit splits too: a shared device gives them a form that does not wait, or refuses them
+            assert p["waits"] == 0, why
+    terms, srcs = {s[0] for s in seen}, {s[1] for s in seen}
+    assert terms == {"t64", "r8", "w8", "kq"} and srcs == {"given", "resident", "reencoded", "relaid"}, seen
+    assert any(s[2] for s in seen) == owned and any(s[3] for s in seen) == owned, seen      # (the grid reaches the one-launch step and the waiting splits where they may exist)
+
+
+def test_no_route_probe_is_left_in_the_kernel_library():
+    """the armed probe (a thread-local switch that made the launcher return in front of its first side effect) is gone: the queries read the plan"""
+    csrc = os.path.join(ROOT, "ggml_amd", "csrc")
+    for d, _, files in os.walk(csrc):
+        for f in files:
+            text = open(os.path.join(d, f), errors="replace").read()
+            assert "g_probe" not in text and "ROUTE_END" not in text, os.path.join(d, f)
+
+
 def test_hardware_verified_kernels_are_unchanged():
     """tools/isa_manifest.py: the ISA of every kernel that was part of a build with a green hardware session (profiles/rNN/isa_manifest.json,
     `hw`: true) is what hipcc emits for it today — so what was added since (listed there as `hw`: false, or new) cannot have changed the

@@ -38,6 +38,7 @@
 #endif
 
 // ---- the HIP runtime calls the library's host code makes
+static inline bool emu_no_run() { static const bool v = getenv("EMU_NO_RUN") && atoi(getenv("EMU_NO_RUN")) != 0; return v; }      // host code only: a launch returns at once and fresh (zeroed) scratch is not filled again (lib_emul plan)
 struct hipDeviceProp_t { int multiProcessorCount; };
 #define hipMemcpyDeviceToDevice 0
 #define hipMemcpyDeviceToHost 0
@@ -49,7 +50,7 @@ static inline hipError_t hipFree(void *) { return 0; }
 #define hipHostMallocMapped 2
 static inline hipError_t hipHostMalloc(void **p, size_t n, int) { *p = emu_shared_alloc(n); return 0; }      // (the fault word: shared with the work-group processes)
 static inline hipError_t hipHostGetDevicePointer(void **d, void *h, int) { *d = h; return 0; }                                  // (guard-paged mappings are left in place)
-static inline hipError_t hipMemset(void *d, int v, size_t n) { memset(d, v, n); return 0; }
+static inline hipError_t hipMemset(void *d, int v, size_t n) { if (!emu_no_run()) memset(d, v, n); return 0; }
 static inline hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t) { memset(d, v, n); return 0; }
 static inline hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, int, hipStream_t) { memmove(d, s, n); return 0; }
 static inline hipError_t hipDeviceSynchronize() { return 0; }
@@ -60,6 +61,7 @@ static inline hipError_t hipGetDeviceProperties(hipDeviceProp_t *p, int) { const
 // ---- kernel launch: every work-group a process (all of a launch at once up to 48 work-groups, so that work-groups that wait for each other
 // are co-resident; larger grids in batches of 16 — the launchers only pair work-groups on grids that fit the chip, see EMU_CUS)
 template <typename F> static void emu_launch(F body, dim3 grid, dim3 block) {
+    if (emu_no_run()) return;
     emu::g_gridDim = grid; emu::g_blockDim = block;
     const int nthreads = (int)(block.x * block.y * block.z);
     const unsigned total = grid.x * grid.y * grid.z, batch = total <= 48 ? total : 16;

@@ -128,6 +128,25 @@ def mul_mat_id(t, m, k, n_expert, n_used, n_b, n_tok, seed=1, cus=256, timeout=1
     return (e, y) if want_y else e
 
 
+def plan(calls, cus=256, env=None):
+    """the prefill GEMM's routing plans (gemm_q_plan.hpp: gemm_q_make_plan through `lib_emul plan`; no kernel runs).  calls: tuples (type, M, K, B, splitk, variant,
+    w_offset, xf, image) — see lib_emul_main.cpp; env: routing knobs (GGML_CDNA4_OWNED_DEVICE, CDNA4_NO_R8, ..).  Returns one dict per call: the plan's fields (numbers as
+    int), `line` (the fields as printed), `pure`, `plan_err` (the plan named the very message the call failed with), `rc` and `msg` of cdna4_launch_gemm_q on the same arguments"""
+    knobs = ("GGML_CDNA4_OWNED_DEVICE", "GGML_CDNA4_SHARED_DEVICE", "CDNA4_NO_R8", "CDNA4_NO_FUSEQ", "CDNA4_T64_HANDOFF", "CDNA4_W8_HANDOFF", "CDNA4_FQ_TICKETED", "EMU_NO_RUN")
+    r = subprocess.run([build(), "plan"], input="".join(" ".join(str(int(x)) for x in c) + "\n" for c in calls), capture_output=True, text=True, timeout=600,
+                       env=dict({k: v for k, v in os.environ.items() if k not in knobs}, EMU_CUS=str(cus), **(env or {})))
+    assert r.returncode == 0, (r.returncode, r.stderr[-800:])
+    lines = r.stdout.splitlines()
+    assert len(lines) == len(calls), (len(lines), len(calls))
+    out = []
+    for ln in lines:
+        fields, msg = ln.split(" | ", 1) if " | " in ln else (ln.rstrip(" |"), "")
+        d = {k: (int(v) if v.lstrip("-").isdigit() else v) for k, v in (f.split("=") for f in fields.split())}
+        d["line"] = fields[:fields.index(" pure=")]; d["msg"] = msg
+        out.append(d)
+    return out
+
+
 if __name__ == "__main__":
     a = [int(v) for v in sys.argv[1:]]
     t, m, k, b = a[:4] if len(a) >= 4 else (R.Q4_1, 130, 768, 33)

@@ -1,8 +1,12 @@
 // lib_emul_main.cpp — driver of the whole-library emulation build (lib_emul.h): calls the library's C-ABI like a host would.  Test infrastructure.
 //   lib_emul mul_mat type M K B path w.bin x.bin y.bin          ggml_cdna4_mul_mat (path 0 = auto, 1 = GEMV, 2 = GEMM); w = M contiguous rows, x = [B][K] f32, y = [B][M]
 //   lib_emul mul_mat_id type M K n_expert n_used n_b n_tok w.bin x.bin ids.bin y.bin
+//   lib_emul plan < calls                                      the prefill GEMM's routing plans (gemm_q_plan.hpp), no kernel runs: see below
 #include "lib_emul.h"
 #include "../../include/ggml_cdna4.h"
+#include "gemm_q_plan.hpp"
+#include <string>
+int cdna4_set_error_msg(const char *msg);
 
 namespace emu {
 thread_local dim3 t_threadIdx, t_blockIdx;
@@ -78,6 +82,44 @@ int main(int argc, char **argv) {
         store(argv[12], y, (size_t)(M * NU * NT) * 4);
         return 0;
     }
-    fprintf(stderr, "usage: lib_emul mul_mat type M K B path w.bin x.bin y.bin | lib_emul mul_mat_id type M K n_expert n_used n_b n_tok w.bin x.bin ids.bin y.bin\n");
+    if (argc >= 2 && !strcmp(argv[1], "plan")) {
+        // one line per call read from stdin, "type M K B splitk variant w_offset xf image": the prefill GEMM's plan (gemm_q_make_plan) as field=value, made twice (`pure`: both
+        // equal and ggml_cdna4_last_error untouched), then what cdna4_launch_gemm_q answers with every launch a no-op (rc, and the message behind `|`).  Operands are addresses
+        // without memory behind them: W = 4096 + w_offset (image != 0: with a resident image registered for it), the activation image and — xf != 0 — the fp32 rows aligned
+        setenv("EMU_NO_RUN", "1", 1);
+        auto line_of = [](const gemm_q_plan &pl) {
+            static const char *src[] = {"given", "resident", "reencoded", "relaid"}, *term[] = {"none", "t64", "r8", "w8", "kq"};
+            const bool t = pl.terminal == GQ_T64, r = pl.terminal == GQ_R8, w = pl.terminal == GQ_W8, q = pl.terminal == GQ_KQ;
+            const int tiles_w8 = ((pl.k.M + 127) / 128) * ((pl.k.B + 127) / 128);
+            char b[512];
+            snprintf(b, sizeof b, "ok=%d kernel=%d route=%d reenc=%d tail=%d fq=%d src=%s wtype=%d wrow=%lld kmul=%d term=%s tm=%d splitk=%d ntiles=%d ticketed=%d waits=%d zero=%d opt=%d sb_split=%d xchg_l2=%d",
+                     !pl.err, pl.kernel, gemm_q_route_id(pl), (int)pl.reencoded, (int)pl.tail_in_store, (int)pl.fuses_quantizer, src[pl.source], w ? pl.w8.type : pl.k.type, (long long)pl.k.w_row_bytes, pl.kmul,
+                     pl.err ? "none" : term[pl.terminal], t ? pl.t64.tm : (r ? pl.r8.tm : (w || q ? 128 : 0)), t ? pl.t64.splitk : (r ? pl.r8.splitk : (w ? pl.w8.splitk : (q ? pl.kq.splitk : 0))),
+                     t ? pl.t64.ntiles : (r ? pl.r8.ntiles : (w || q ? tiles_w8 : 0)), t ? (int)pl.t64.ticketed2 : (w ? (int)pl.w8.ticketed : 0),
+                     t ? (pl.t64.fq || (pl.t64.splitk == 2 && !pl.t64.ticketed2)) : (r ? pl.r8.splitk > 1 : (w ? pl.w8.exchange && !pl.w8.ticketed : 0)),
+                     w ? (pl.w8.splitk > 1 && !pl.w8.exchange) : (q ? pl.kq.splitk > 1 : 0), w ? pl.w8.opt : 0, w ? pl.w8.sb_split : 0, w ? pl.w8.xchg_l2 : 0);
+            return std::string(b);
+        };
+        char in[256];
+        while (fgets(in, sizeof in, stdin)) {
+            long long v[9] = {0};
+            if (sscanf(in, "%lld %lld %lld %lld %lld %lld %lld %lld %lld", v, v + 1, v + 2, v + 3, v + 4, v + 5, v + 6, v + 7, v + 8) < 6) continue;
+            cdna4_gemm_args a{};
+            a.type = (int)v[0]; a.M = (int)v[1]; a.K = (int)v[2]; a.B = (int)v[3]; a.splitk = (int)v[4]; a.variant = (int)v[5];
+            a.W = (const uint8_t *)(uintptr_t)(4096 + v[6]); a.w_row_bytes = (int64_t)ggml_cdna4_row_size(a.type, a.K);
+            a.xh = (const void *)(uintptr_t)(1 << 20); a.xh_row_elems = a.K; a.y_row_elems = a.M;
+            if (v[7]) { a.xf = (const float *)(uintptr_t)(1 << 21); a.xf_row_elems = a.K; }
+            if (v[8]) cdna4_resident_register(a.type, a.W, a.w_row_bytes, a.M, a.K, (const void *)(uintptr_t)(1 << 22));
+            cdna4_set_error_msg("untouched");
+            const std::string l1 = line_of(gemm_q_make_plan(a)), l2 = line_of(gemm_q_make_plan(a));
+            const bool pure = l1 == l2 && !strcmp(ggml_cdna4_last_error(), "untouched");
+            const gemm_q_plan pl = gemm_q_make_plan(a);
+            const int rc = cdna4_launch_gemm_q(a, nullptr);
+            printf("%s pure=%d plan_err=%d rc=%d | %s\n", l1.c_str(), (int)pure, (int)(pl.err != nullptr && !strcmp(pl.err, ggml_cdna4_last_error())), rc, rc ? ggml_cdna4_last_error() : "");
+            if (v[8]) cdna4_resident_unregister(a.W);
+        }
+        return 0;
+    }
+    fprintf(stderr, "usage: lib_emul mul_mat type M K B path w.bin x.bin y.bin | lib_emul mul_mat_id type M K n_expert n_used n_b n_tok w.bin x.bin ids.bin y.bin | lib_emul plan < calls\n");
     return 2;
 }

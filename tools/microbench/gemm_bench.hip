@@ -34,7 +34,7 @@ int main(int argc, char **argv) {
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     struct cfg { int variant, splitk, ablate; };
     std::vector<cfg> cfgs;
-    // GB_VARIANTS="23,55,151" overrides the variant list (see launch_type() in gemm_q_mfma.hip for the bits)
+    // GB_VARIANTS="23,55,151" overrides the variant list (see plan_type() in gemm_q_mfma.hip for the bits)
     std::vector<int> vars = {0, 5, 663};
     if (const char *e = getenv("GB_VARIANTS")) { vars.clear(); for (const char *q = e; *q;) { vars.push_back(atoi(q)); while (*q && *q != ',') q++; if (*q) q++; } }
     std::vector<int> sks = {1, 2};
