@@ -4,6 +4,7 @@
 #include "cdna4_formats.hpp"
 #include "cdna4_kernels.h"
 #include "gemm_q_plan.hpp"
+#include "mul_mat_id_plan.hpp"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -66,13 +67,9 @@ static moe_sk_view moe_sk_carve(int64_t K, int64_t n_expert, int64_t n_used, int
     v.total = off;
     return v;
 }
-// does ggml_cdna4_mul_mat_id take the stream-k form for this call?  Q4_K experts (Q4_0 with a resident image asks with CDNA4_Q4_0R); CDNA4_MOE_SK=0: the per-tile launches
-static bool moe_sk_on(int type, int64_t M, int64_t K, int64_t n_expert, int64_t n_used, int64_t n_b, int64_t n_tok) {
-    static const bool off = getenv("CDNA4_MOE_SK") && atoi(getenv("CDNA4_MOE_SK")) == 0;
-    if (off || n_expert > 1024) return false;
-    const moe_sk_view v = moe_sk_carve(K, n_expert, n_used, n_b, n_tok, nullptr);
-    return cdna4_gemm_sk_supported(type, M, K, v.n_rows, v.ntile_cap);
-}
+// may a MUL_MAT_ID of this type / K / expert count take the work-queue form?  (Q4_K experts, or Q4_0 experts in case their stack has a resident Q4_0R image: the plan
+// and the workspace size both ask here)
+static bool mmid_queue_shape(int type, int64_t K, int64_t n_expert) { return (type == CDNA4_Q4_K || type == CDNA4_Q4_0) && K % 256 == 0 && n_expert <= 1024; }
 
 extern "C" {
 
@@ -133,7 +130,7 @@ size_t ggml_cdna4_mul_mat_id_workspace_size(int type, int64_t K, int64_t n_exper
     if (!cdna4_gemm_ids_supported(type, K) || n_tok * n_used <= 32) return plain;
     size_t grouped = moe_carve(K, n_expert, n_used, n_tok, nullptr).total;
     // (the stream-k form's carve — Q4_K, and Q4_0 in case its stack has a resident image; M is not known here: its tables do not depend on it)
-    if ((type == CDNA4_Q4_K || type == CDNA4_Q4_0) && K % 256 == 0 && n_expert <= 1024) { const size_t sk = moe_sk_carve(K, n_expert, n_used, n_b, n_tok, nullptr).total; if (sk > grouped) grouped = sk; }
+    if (mmid_queue_shape(type, K, n_expert)) { const size_t sk = moe_sk_carve(K, n_expert, n_used, n_b, n_tok, nullptr).total; if (sk > grouped) grouped = sk; }
     return grouped > plain ? grouped : plain;
 }
 
@@ -518,152 +515,180 @@ int ggml_cdna4_mul_mat_prepared_fused(int type, const void *W, int64_t w_row_byt
     return mul_mat_impl(type, W, w_row_bytes, nullptr, 0, Y, y_row_stride, M, K, B, (void *)workspace, workspace_bytes, GGML_CDNA4_PATH_AUTO, 0, 0, e, stream);
 }
 
-// the resident Q4_0R image of a Q4_0 expert stack (ggml's 3-D expert tensor: the experts' rows back to back; found by the stack's pointer, like ggml_cdna4_mul_mat finds a
-// matrix's), or nullptr: with it the stack runs on Q4_K's grouped kernels (row stride (K / 256) * 144)
-static const uint8_t *moe_q4_0r_image(int type, const void *as, int64_t w_row_bytes, int64_t w_expert_bytes, int64_t M, int64_t K, int64_t n_expert) {
-    if (type != CDNA4_Q4_0 || K % 256 || w_expert_bytes != M * w_row_bytes) return nullptr;
-    const uint8_t *img = cdna4_resident_lookup(CDNA4_Q4_0, as, w_row_bytes, M * n_expert, K);
-    return img && !((uintptr_t)img & 15) ? img : nullptr;
+}  // extern "C"
+
+// ---- The routing plan of a MUL_MAT_ID (mul_mat_id_plan.hpp): the ONE place that decides which launches a call takes.  ggml_cdna4_mul_mat_id and its
+// `prepared` twin execute it, ggml_cdna4_mul_mat_id_front_key reads its key: change the routing here and nowhere else.
+struct mmid_knobs {                               // read once per process
+    bool sk_off;                                  // CDNA4_MOE_SK=0: the per-tile launches instead of the work-queue form
+    bool no_mmq_ids, mmq_ids_all;                 // CDNA4_NO_MMQ_IDS=1: no int8 matrix-core route; CDNA4_MMQ_IDS=2 (coverage / measurement): that route for Q4_K too, in front of the work queue
+    // cost of one (tile, m-tile, superblock) unit by the tile's fragments in use (1 .. 4), relative.  FLAT, by measurement: the k loop is bound by its unpack /
+    // issue work, which does not depend on the fragments — a tile with one fragment in use takes 1.78-1.91 us per superblock, a full one 1.86-1.92
+    // (profiles/r06/moe_sk_trace_*.txt), with or without the activation DMA of the empty fragments; weights that call light tiles cheaper lost: 8 x 2 x 512 x 4096^2,
+    // us per call, one box: 10,10,10,10 72.2 | 8,9,10,10 79.8 | 7,8,9,10 85.0 | 6,8,9,10 90.7 | 5,7,9,10 98.1 | 4,6,8,10 107.6 (CDNA4_SK_CW=a,b,c,d: measurement knob)
+    int cw[4];
+    mmid_knobs() : cw{10, 10, 10, 10} {
+        const auto num = [](const char *e, int dflt) { return e ? atoi(e) : dflt; };
+        sk_off = num(getenv("CDNA4_MOE_SK"), 1) == 0; no_mmq_ids = num(getenv("CDNA4_NO_MMQ_IDS"), 0) != 0; mmq_ids_all = num(getenv("CDNA4_MMQ_IDS"), 0) == 2;
+        int t4[4]; const char *ev = getenv("CDNA4_SK_CW");
+        if (ev && sscanf(ev, "%d,%d,%d,%d", &t4[0], &t4[1], &t4[2], &t4[3]) == 4 && t4[0] > 0 && t4[1] > 0 && t4[2] > 0 && t4[3] > 0 && t4[3] < 256) for (int i = 0; i < 4; i++) cw[i] = t4[i];
+    }
+};
+static const char *const mmid_no_front = "mul_mat_id_prepared: a call of this shape leaves no front (ggml_cdna4_mul_mat_id_front_key == 0)";
+mmid_plan mmid_make_plan(const mmid_call &c, bool front_in_place) {
+    static const mmid_knobs knobs;
+    mmid_plan p{};
+    p.w_type = c.type; p.W = (const uint8_t *)c.as; p.w_row_bytes = c.w_row_bytes; p.w_expert_bytes = c.w_expert_bytes;
+    const auto refuse = [&p](int rc, const char *msg) { p.kind = MMID_REFUSED; p.rc = rc; p.err = msg; return p; };
+    const int type = c.type; const int64_t M = c.M, K = c.K, pairs = c.n_tok * c.n_used;
+    const uintptr_t w_bits = (uintptr_t)c.as | (uintptr_t)c.w_row_bytes | (uintptr_t)c.w_expert_bytes, b_bits = (uintptr_t)c.b | (uintptr_t)(c.b_row_stride * 4);
+    const bool kq = cdna4_type_is_kq(type), w16 = !(w_bits & 15), ws_ok = c.workspace && !((uintptr_t)c.workspace & 255);
+    // prefill-sized mixture-of-experts batches: group the (token, slot) rows by expert on the device and run ONE MFMA GEMM launch over
+    // the (expert, activation tile) table — every expert's weights are read once per m-tile instead of once per column
+    // (ggml_compute_forward_mul_mat_id groups the same way on the host: ggml-cpu.c:7648-7781)
+    const bool big = cdna4_type_qk(type) && M > 0 && K > 0 && c.n_tok > 0 && c.n_used > 0 && c.n_b > 0 && c.n_used % c.n_b == 0 && ggml_cdna4_row_size(type, K) != 0 &&
+                     cdna4_gemm_ids_supported(type, K) && pairs > 32 && c.n_expert <= 1024 && !(w_bits & 1);
+    // the resident Q4_0R image of a Q4_0 expert stack (ggml's 3-D expert tensor: the experts' rows back to back; found by the stack's pointer, like ggml_cdna4_mul_mat finds a
+    // matrix's), or nullptr: with it the stack runs on Q4_K's grouped kernels (row stride (K / 256) * 144)
+    const uint8_t *img = big && type == CDNA4_Q4_0 && K % 256 == 0 && c.w_expert_bytes == M * c.w_row_bytes ? cdna4_resident_lookup(CDNA4_Q4_0, c.as, c.w_row_bytes, M * c.n_expert, K) : nullptr;
+    if ((uintptr_t)img & 15) img = nullptr;
+    const auto reads_image = [&p, img, M, K] { p.w_type = CDNA4_Q4_0R; p.W = img; p.w_row_bytes = (K / 256) * 144; p.w_expert_bytes = M * p.w_row_bytes; };
+    // Q4_K experts, and Q4_0 experts whose stack has a RESIDENT Q4_0R image: the work-queue (stream-k) form — TWO launches (planner + token-order quantizer; one persistent
+    // grouped GEMM that gathers its rows), round 6.  By everything but b, the strides and the workspace pointer: what the key answers from
+    const moe_sk_view sv = moe_sk_carve(K, c.n_expert, c.n_used, c.n_b, c.n_tok, nullptr);
+    const bool queue = big && mmid_queue_shape(type, K, c.n_expert) && (img || (type == CDNA4_Q4_K && w16)) && !knobs.sk_off && !(knobs.mmq_ids_all && pairs <= 32 * c.n_expert) &&
+                       cdna4_gemm_sk_supported(img ? CDNA4_Q4_0R : CDNA4_Q4_K, M, K, sv.n_rows, sv.ntile_cap) && c.workspace_bytes >= sv.total;
+    if (front_in_place && !queue) return refuse(-2, mmid_no_front);
+    if (!cdna4_type_qk(type)) return refuse(-1, "mul_mat_id: unsupported weight type");
+    if (M <= 0 || c.n_tok <= 0 || c.n_used <= 0) { p.kind = MMID_EMPTY; return p; }
+    if (K <= 0 || ggml_cdna4_row_size(type, K) == 0) return refuse(-1, "mul_mat_id: K is not a whole number of blocks");
+    if (c.n_b <= 0 || c.n_used % c.n_b) return refuse(-1, "mul_mat_id: n_used must be a multiple of b.ne[1]");   // ggml_mul_mat_id: ids->ne[0] % b->ne[1] == 0 (src/ggml.c:2747); slot u reads row u % n_b
+    if (c.dst_tok_stride != c.n_used * c.dst_row_stride) return refuse(-1, "mul_mat_id: dst must be contiguous over (slot, token)");
+    if (c.b_tok_stride != c.n_b * c.b_row_stride) return refuse(-1, "mul_mat_id: b must be contiguous over (row, token)");
+    const bool grouped = big && ws_ok && !(b_bits & 15);
+    if (front_in_place && !grouped) return refuse(-2, "mul_mat_id_prepared: misaligned operands");
+    if (grouped && queue) {
+        p.kind = MMID_QUEUE; p.ws_need = sv.total; p.rows = sv.n_rows; p.ntile_cap = sv.ntile_cap; p.front_in_place = front_in_place;
+        if (img) reads_image();
+        p.G = cdna4_gemm_sk_spans(); p.upt = ((M + 127) / 128) * (K / 256);
+        for (int i = 0; i < 4; i++) p.cw[i] = knobs.cw[i];
+        p.front_key = 0x4D510000u | (img ? 2u : 1u);                    // (the image's activation class; the rest of what the front depends on is what the caller compares)
+        return p;
+    }
+    const moe_view mv = moe_carve(K, c.n_expert, c.n_used, c.n_tok, nullptr);
+    if (grouped && c.workspace_bytes >= mv.total && mv.img_rows * K * 2 < ((int64_t)1 << 31)) {      // (a workspace below that: the GEMV forms)
+        p.ws_need = mv.total; p.rows = mv.img_rows;
+        // few rows per expert (on average at most 32): the int8 matrix-core kernel over 32-row chunks of the same expert-sorted image — the CPU's own integer
+        // block dots (ggml_compute_forward_mul_mat_id's vec_dot calls, ggml-cpu.c:7752-7776) instead of fp16 tiles that would be mostly padding.  The int8
+        // image (quants, d, bsums) takes the place of the fp16 one in the workspace.  Where it wins (MI355X, one box, 8 experts x 2 used x 4096^2, us per call at
+        // 32 / 64 / 128 tokens, profiles/r04/moe64_ab.txt): Q6_K 95 / 96 / 125 vs 158 / 158 / 160 and Q8_0 91 / 92 / 133 vs 144 / 144 / 147 on the grouped per-lane-load
+        // GEMM these formats have; NOT Q4_K, whose grouped k_gemm_kq_t64 takes 45 / 46 / 51 against 82 / 83 / 115 (CDNA4_MMQ_IDS=2 forces it there: 2e-7 from the
+        // oracle instead of 3e-4).  CDNA4_NO_MMQ_IDS=1 turns the route off.
+        if (!knobs.no_mmq_ids && (type != CDNA4_Q4_K || knobs.mmq_ids_all) && pairs <= 32 * c.n_expert && cdna4_mmq_ids_supported(type, K) && !(w_bits & (type == CDNA4_Q6_K ? 1 : 15))) {
+            p.kind = MMID_TILES_MMQ;
+        } else if (img || (type == CDNA4_Q4_K && w16)) {                 // Q4_0 experts with a resident image of the whole stack: Q4_K's grouped kernel (round 5)
+            p.kind = MMID_TILES_T64; p.t64 = t64_ids_make_plan((int)M, (int)K, (int)mv.img_rows);
+            if (img) reads_image();
+        } else {                                                          // Q5_K / Q6_K / Q4_0 / Q8_0, and Q4_K rows the 16-byte loads cannot take
+            p.kind = MMID_TILES_KQ; p.wlds = cdna4_gemm_ids_wlds(type, c.as, c.w_row_bytes, c.w_expert_bytes);
+        }
+        return p;
+    }
+    // the GEMV forms, column c = (token, slot).  One token: one launch, the activation quantizer runs inside the GEMV
+    const bool one = c.n_tok == 1 && c.n_used <= 65535 && cdna4_gemv_fused_supported(type, K, 1) && !(b_bits & 15);
+    if (!one) {
+        if (!ws_ok) return refuse(-1, "mul_mat_id: workspace must be 256-byte aligned");
+        p.ws_need = carve(type, K, c.n_tok * c.n_b, nullptr).total; p.rows = c.n_tok * c.n_b;
+        if (c.workspace_bytes < p.ws_need) return refuse(-1, "mul_mat_id: workspace too small");
+        if (b_bits & 15) return refuse(-1, kq ? "quantize_q8_K: x must be 16-byte aligned" : (cdna4_is_q81(type) ? "quantize_q8_1: x must be 16-byte aligned" : "quantize_q8_0: x must be 16-byte aligned"));
+    }
+    // (what the activation quantizers and the GEMV launchers refuse, named here so that the call fails in front of its quantizer launch, not behind it.  The launchers
+    //  remain the authority — ggml_cdna4_quantize_q8_* above, gemv_q.hip: cdna4_launch_gemv_q / _fused_ids, gemv_operands_ok — and keep their checks: these lines must MIRROR
+    //  them, message for message; the property test over the call grid compares the plan's refusal with what the call answers)
+    if (((uintptr_t)c.as | (uintptr_t)c.w_row_bytes | (uintptr_t)(one ? c.w_expert_bytes : 0)) & 1) return refuse(-1, "gemv_q: misaligned operands");
+    if (!one && pairs > 65535) return refuse(-1, "gemv_q: too many MUL_MAT_ID columns");
+    if ((type == CDNA4_Q4_K || type == CDNA4_Q5_K) && !w16) return refuse(-1, "gemv_q: Q4_K/Q5_K rows must be 16-byte aligned");
+    p.kind = one ? MMID_GEMV_1 : MMID_GEMV;
+    return p;
 }
-// the work-queue form's choice for a call (shared by the call, its `prepared` twin and the key): Q4_K experts, or Q4_0 experts whose stack has a resident Q4_0R image
-struct moe_sk_pick { int type = -1; const uint8_t *W = nullptr; int64_t row = 0, exp = 0; };
-static moe_sk_pick moe_sk_pick_of(int type, const void *as, int64_t w_row_bytes, int64_t w_expert_bytes, int64_t M, int64_t K, int64_t n_expert, int64_t n_used, int64_t n_b, int64_t n_tok) {
-    moe_sk_pick r; r.W = (const uint8_t *)as; r.row = w_row_bytes; r.exp = w_expert_bytes;
-    if (type == CDNA4_Q4_K && !(((uintptr_t)as | (uintptr_t)w_row_bytes | (uintptr_t)w_expert_bytes) & 15)) r.type = CDNA4_Q4_K;
-    else if (const uint8_t *img = moe_q4_0r_image(type, as, w_row_bytes, w_expert_bytes, M, K, n_expert)) { r.type = CDNA4_Q4_0R; r.W = img; r.row = (K / 256) * 144; r.exp = M * r.row; }
-    // (CDNA4_MMQ_IDS=2 — a coverage / measurement knob — asks for the int8 matrix-core kernels where there are few rows per expert)
-    static const bool mmq_ids_forced = getenv("CDNA4_MMQ_IDS") && atoi(getenv("CDNA4_MMQ_IDS")) == 2;
-    if (mmq_ids_forced && n_tok * n_used <= 32 * n_expert) r.type = -1;
-    if (r.type >= 0 && !moe_sk_on(r.type, M, K, n_expert, n_used, n_b, n_tok)) r.type = -1;
-    return r;
+
+static int mul_mat_id_impl(const mmid_call &c, bool front_in_place, void *stream) {
+    if (const int frc = fault_status()) return frc;
+    const mmid_plan p = mmid_make_plan(c, front_in_place);
+    if (p.kind == MMID_REFUSED) { cdna4_set_error_msg(p.err); return p.rc; }
+    hipStream_t st = (hipStream_t)stream;
+    const bool kq = cdna4_type_is_kq(c.type);
+    // the MUL_MAT_ID columns of a GEMV launch
+    const auto gemv_ids = [&c](cdna4_gemv_args g) {
+        g.ids = c.ids; g.ids_tok_stride = c.ids_tok_stride; g.w_expert_bytes = c.w_expert_bytes; g.n_used = (int)c.n_used; g.n_b = (int)c.n_b; g.n_expert = (int)c.n_expert;
+        return g;
+    };
+    switch (p.kind) {
+    case MMID_QUEUE: {
+        const moe_sk_view sv = moe_sk_carve(c.K, c.n_expert, c.n_used, c.n_b, c.n_tok, c.workspace);
+        // (prepared: the front of an earlier call with the same b, ids and shape is in place)
+        if (!p.front_in_place)
+            if (const int rc = cdna4_launch_moe_sk_front(c.ids, c.ids_tok_stride, (int)c.n_tok, (int)c.n_used, (int)c.n_b, (int)c.n_expert, (int)p.ntile_cap, (int)p.upt, p.G, p.cw,
+                                                         sv.tile_rec, sv.wg_begin, c.b, c.b_row_stride, c.K, p.w_type == CDNA4_Q4_K, sv.xh, st)) return rc;
+        const cdna4_gemm_args a = gemm_args_of(p.w_type, p.W, p.w_row_bytes, sv.xh, c.dst, c.dst_row_stride, c.M, c.K, p.rows, 0, 0, cdna4_epilogue{});
+        return cdna4_launch_gemm_sk(a, sv.tile_rec, sv.wg_begin, p.G, p.w_expert_bytes, st);
+    }
+    case MMID_TILES_MMQ: case MMID_TILES_T64: case MMID_TILES_KQ: {
+        const moe_view mv = moe_carve(c.K, c.n_expert, c.n_used, c.n_tok, c.workspace);
+        int rc = cdna4_launch_moe_plan(c.ids, c.ids_tok_stride, (int)c.n_tok, (int)c.n_used, (int)c.n_b, (int)c.n_expert, (int)mv.img_rows, mv.img_src, mv.img_dst, mv.tile_expert, st);
+        if (rc) return rc;
+        if (p.kind == MMID_TILES_MMQ) {
+            ws_view iv{};                                                // the int8 image: [qs][d][bsums (K-quants)]
+            iv.qs = (int8_t *)mv.xh;
+            iv.d = (float *)((uint8_t *)mv.xh + align256((size_t)mv.img_rows * c.K));
+            iv.bsums = kq ? (int16_t *)((uint8_t *)iv.d + align256((size_t)mv.img_rows * (c.K / 32) * 4)) : nullptr;
+            rc = kq ? cdna4_launch_quantize_q8_K_gather_i8(c.b, c.b_row_stride, c.K, mv.img_rows, mv.img_src, iv.qs, iv.d, iv.bsums, st)
+                    : cdna4_launch_quantize_q8_0_gather_i8(c.b, c.b_row_stride, c.K, mv.img_rows, mv.img_src, iv.qs, iv.d, st);
+            if (rc) return rc;
+            return cdna4_launch_mmq_ids(gemv_args_of(p.w_type, p.W, p.w_row_bytes, iv, c.dst, c.dst_row_stride, c.M, c.K, mv.img_rows, cdna4_epilogue{}), mv.tile_expert, mv.img_dst, p.w_expert_bytes, st);
+        }
+        rc = kq ? cdna4_launch_quantize_q8_K_gather(c.b, c.b_row_stride, c.K, mv.img_rows, mv.img_src, mv.xh, st)
+                : cdna4_launch_quantize_q8_0_gather(c.b, c.b_row_stride, c.K, mv.img_rows, mv.img_src, mv.xh, st);
+        if (rc) return rc;
+        const cdna4_gemm_args a = gemm_args_of(p.w_type, p.W, p.w_row_bytes, mv.xh, c.dst, c.dst_row_stride, c.M, c.K, mv.img_rows, 0, 0, cdna4_epilogue{});
+        return p.kind == MMID_TILES_T64 ? cdna4_launch_gemm_t64_ids(a, mv.tile_expert, mv.img_dst, p.w_expert_bytes, st) : cdna4_launch_gemm_ids(a, mv.tile_expert, mv.img_dst, p.w_expert_bytes, st);
+    }
+    case MMID_GEMV_1:
+        return cdna4_launch_gemv_q_fused_ids(gemv_ids(gemv_args_of(c.type, c.as, c.w_row_bytes, ws_view{}, c.dst, c.dst_row_stride, c.M, c.K, c.n_used, cdna4_epilogue{})), c.b, c.b_row_stride, st);
+    case MMID_GEMV: {
+        const ws_view v = carve(c.type, c.K, p.rows, c.workspace);
+        if (const int rc = ggml_cdna4_prepare_act(c.type, c.b, c.b_row_stride, c.K, p.rows, c.workspace, c.workspace_bytes, GGML_CDNA4_PATH_GEMV, stream)) return rc;
+        return cdna4_launch_gemv_q(gemv_ids(gemv_args_of(c.type, c.as, c.w_row_bytes, v, c.dst, c.dst_row_stride, c.M, c.K, c.n_tok * c.n_used, cdna4_epilogue{})), st);
+    }
+    default: return 0;                                                   // MMID_EMPTY
+    }
 }
-static bool moe_grouped_call(int type, const void *as, int64_t w_row_bytes, int64_t w_expert_bytes, const float *b, int64_t b_row_stride, int64_t K, int64_t n_expert, int64_t n_used, int64_t n_tok, const void *workspace) {
-    return cdna4_gemm_ids_supported(type, K) && n_tok * n_used > 32 && n_expert <= 1024 && workspace && !((uintptr_t)workspace & 255) &&
-           !(((uintptr_t)as | (uintptr_t)w_row_bytes | (uintptr_t)w_expert_bytes) & 1) && !(((uintptr_t)b | (uintptr_t)(b_row_stride * 4)) & 15);
-}
-static int mul_mat_id_impl(bool front_in_place, int type, const void *as, int64_t w_row_bytes, int64_t w_expert_bytes, const float *b, int64_t b_row_stride, int64_t b_tok_stride,
-                           const int32_t *ids, int64_t ids_tok_stride, float *dst, int64_t dst_row_stride, int64_t dst_tok_stride,
-                           int64_t M, int64_t K, int64_t n_expert, int64_t n_used, int64_t n_b, int64_t n_tok,
-                           void *workspace, size_t workspace_bytes, void *stream);
+
+extern "C" {
+
 int ggml_cdna4_mul_mat_id(int type, const void *as, int64_t w_row_bytes, int64_t w_expert_bytes, const float *b, int64_t b_row_stride, int64_t b_tok_stride,
                           const int32_t *ids, int64_t ids_tok_stride, float *dst, int64_t dst_row_stride, int64_t dst_tok_stride,
                           int64_t M, int64_t K, int64_t n_expert, int64_t n_used, int64_t n_b, int64_t n_tok,
                           void *workspace, size_t workspace_bytes, void *stream) {
-    return mul_mat_id_impl(false, type, as, w_row_bytes, w_expert_bytes, b, b_row_stride, b_tok_stride, ids, ids_tok_stride, dst, dst_row_stride, dst_tok_stride, M, K, n_expert, n_used, n_b, n_tok,
-                           workspace, workspace_bytes, stream);
+    const mmid_call c = {type, as, w_row_bytes, w_expert_bytes, b, b_row_stride, b_tok_stride, ids, ids_tok_stride, dst, dst_row_stride, dst_tok_stride, M, K, n_expert, n_used, n_b, n_tok, workspace, workspace_bytes};
+    return mul_mat_id_impl(c, false, stream);
 }
 // MUL_MAT_IDs of ONE (b, ids) — a mixture-of-experts layer's w_up and w_gate stacks (llama.cpp build_moe_ffn) — share everything the first launch of the work-queue form makes:
 // the sorted ids, the tile records, the spans, the quantized activations.  Non-zero: a ggml_cdna4_mul_mat_id of this call leaves that FRONT in its workspace, and
 // ggml_cdna4_mul_mat_id_prepared with other expert weights of the same type / M / K, the same b, ids, strides and counts, on the untouched workspace multiplies it again
-// (ONE launch instead of two, bit-identical to the full call).
+// (ONE launch instead of two, bit-identical to the full call).  The key of the plan of this call on aligned, contiguous stand-ins for the operands it is not given.
 uint32_t ggml_cdna4_mul_mat_id_front_key(int type, const void *as, int64_t w_row_bytes, int64_t w_expert_bytes, int64_t M, int64_t K, int64_t n_expert, int64_t n_used, int64_t n_b, int64_t n_tok, size_t workspace_bytes) {
-    if (!cdna4_type_qk(type) || M <= 0 || K <= 0 || n_tok <= 0 || n_used <= 0 || n_b <= 0 || n_used % n_b || ggml_cdna4_row_size(type, K) == 0) return 0;
-    if (!(cdna4_gemm_ids_supported(type, K) && n_tok * n_used > 32 && n_expert <= 1024) || (((uintptr_t)as | (uintptr_t)w_row_bytes | (uintptr_t)w_expert_bytes) & 1)) return 0;
-    const moe_sk_pick pk = moe_sk_pick_of(type, as, w_row_bytes, w_expert_bytes, M, K, n_expert, n_used, n_b, n_tok);
-    if (pk.type < 0 || workspace_bytes < moe_sk_carve(K, n_expert, n_used, n_b, n_tok, nullptr).total) return 0;
-    return 0x4D510000u | (pk.type == CDNA4_Q4_K ? 1u : 2u);            // (the image's activation class; the rest of what the front depends on is what the caller compares)
+    const mmid_call c = {type, as, w_row_bytes, w_expert_bytes, (const float *)(uintptr_t)256, K, n_b * K, nullptr, n_used, nullptr, M, n_used * M, M, K, n_expert, n_used, n_b, n_tok, (void *)(uintptr_t)256, workspace_bytes};
+    return mmid_make_plan(c, false).front_key;
 }
 int ggml_cdna4_mul_mat_id_prepared(int type, const void *as, int64_t w_row_bytes, int64_t w_expert_bytes, const float *b, int64_t b_row_stride, int64_t b_tok_stride,
                                    const int32_t *ids, int64_t ids_tok_stride, float *dst, int64_t dst_row_stride, int64_t dst_tok_stride,
                                    int64_t M, int64_t K, int64_t n_expert, int64_t n_used, int64_t n_b, int64_t n_tok,
                                    void *workspace, size_t workspace_bytes, void *stream) {
-    if (!ggml_cdna4_mul_mat_id_front_key(type, as, w_row_bytes, w_expert_bytes, M, K, n_expert, n_used, n_b, n_tok, workspace_bytes)) { cdna4_set_error_msg("mul_mat_id_prepared: a call of this shape leaves no front (ggml_cdna4_mul_mat_id_front_key == 0)"); return -2; }
-    return mul_mat_id_impl(true, type, as, w_row_bytes, w_expert_bytes, b, b_row_stride, b_tok_stride, ids, ids_tok_stride, dst, dst_row_stride, dst_tok_stride, M, K, n_expert, n_used, n_b, n_tok,
-                           workspace, workspace_bytes, stream);
-}
-static int mul_mat_id_impl(bool front_in_place, int type, const void *as, int64_t w_row_bytes, int64_t w_expert_bytes, const float *b, int64_t b_row_stride, int64_t b_tok_stride,
-                           const int32_t *ids, int64_t ids_tok_stride, float *dst, int64_t dst_row_stride, int64_t dst_tok_stride,
-                           int64_t M, int64_t K, int64_t n_expert, int64_t n_used, int64_t n_b, int64_t n_tok,
-                           void *workspace, size_t workspace_bytes, void *stream) {
-    if (const int frc = fault_status()) return frc;
-    if (!cdna4_type_qk(type)) return cdna4_set_error_msg("mul_mat_id: unsupported weight type");
-    if (M <= 0 || n_tok <= 0 || n_used <= 0) return 0;
-    if (K <= 0 || ggml_cdna4_row_size(type, K) == 0) return cdna4_set_error_msg("mul_mat_id: K is not a whole number of blocks");
-    if (n_b <= 0 || n_used % n_b) return cdna4_set_error_msg("mul_mat_id: n_used must be a multiple of b.ne[1]");   // ggml_mul_mat_id: ids->ne[0] % b->ne[1] == 0 (src/ggml.c:2747); slot u reads row u % n_b
-    if (dst_tok_stride != n_used * dst_row_stride) return cdna4_set_error_msg("mul_mat_id: dst must be contiguous over (slot, token)");
-    if (b_tok_stride != n_b * b_row_stride) return cdna4_set_error_msg("mul_mat_id: b must be contiguous over (row, token)");
-    const int64_t nact = n_tok * n_b;
-    // prefill-sized mixture-of-experts batches: group the (token, slot) rows by expert on the device and run ONE MFMA GEMM launch over
-    // the (expert, activation tile) table — every expert's weights are read once per m-tile instead of once per column
-    // (ggml_compute_forward_mul_mat_id groups the same way on the host: ggml-cpu.c:7648-7781)
-    const bool grouped = moe_grouped_call(type, as, w_row_bytes, w_expert_bytes, b, b_row_stride, K, n_expert, n_used, n_tok, workspace);
-    if (front_in_place && !grouped) { cdna4_set_error_msg("mul_mat_id_prepared: misaligned operands"); return -2; }
-    if (grouped) {
-        // Q4_K experts, and Q4_0 experts whose stack has a RESIDENT Q4_0R image: the stream-k form — TWO launches (planner + token-order quantizer; one persistent grouped
-        // GEMM that gathers its rows), round 6
-        const moe_sk_pick pk = moe_sk_pick_of(type, as, w_row_bytes, w_expert_bytes, M, K, n_expert, n_used, n_b, n_tok);
-        const moe_sk_view sv = moe_sk_carve(K, n_expert, n_used, n_b, n_tok, workspace);
-        if (pk.type >= 0 && workspace_bytes >= sv.total) {
-            // cost of one (tile, m-tile, superblock) unit by the tile's fragments in use (1 .. 4), relative.  FLAT, by measurement: the k loop is bound by its unpack /
-            // issue work, which does not depend on the fragments — a tile with one fragment in use takes 1.78-1.91 us per superblock, a full one 1.86-1.92
-            // (profiles/r06/moe_sk_trace_*.txt), with or without the activation DMA of the empty fragments; weights that call light tiles cheaper lost: 8 x 2 x 512 x 4096^2,
-            // us per call, one box: 10,10,10,10 72.2 | 8,9,10,10 79.8 | 7,8,9,10 85.0 | 6,8,9,10 90.7 | 5,7,9,10 98.1 | 4,6,8,10 107.6 (CDNA4_SK_CW=a,b,c,d: measurement knob)
-            struct sk_costs { int c[4]; sk_costs() : c{10, 10, 10, 10} { int t4[4]; const char *ev = getenv("CDNA4_SK_CW");
-                if (ev && sscanf(ev, "%d,%d,%d,%d", &t4[0], &t4[1], &t4[2], &t4[3]) == 4 && t4[0] > 0 && t4[1] > 0 && t4[2] > 0 && t4[3] > 0 && t4[3] < 256) for (int i = 0; i < 4; i++) c[i] = t4[i]; } };
-            static const sk_costs costs;
-            const int G = cdna4_gemm_sk_spans();
-            const int64_t upt = ((M + 127) / 128) * (K / 256);
-            // (prepared: the front of an earlier call with the same b, ids and shape is in place)
-            const int rc = front_in_place ? 0 : cdna4_launch_moe_sk_front(ids, ids_tok_stride, (int)n_tok, (int)n_used, (int)n_b, (int)n_expert, (int)sv.ntile_cap, (int)upt, G, costs.c,
-                                                                          sv.tile_rec, sv.wg_begin, b, b_row_stride, K, pk.type == CDNA4_Q4_K, sv.xh, (hipStream_t)stream);
-            if (rc) return rc;
-            const cdna4_gemm_args a = gemm_args_of(pk.type, pk.W, pk.row, sv.xh, dst, dst_row_stride, M, K, sv.n_rows, 0, 0, cdna4_epilogue{});
-            return cdna4_launch_gemm_sk(a, sv.tile_rec, sv.wg_begin, G, pk.exp, (hipStream_t)stream);
-        }
-        if (front_in_place) { cdna4_set_error_msg("mul_mat_id_prepared: this call does not take the work-queue form"); return -2; }
-        const moe_view mv = moe_carve(K, n_expert, n_used, n_tok, workspace);
-        if (workspace_bytes >= mv.total && mv.img_rows * K * 2 < ((int64_t)1 << 31)) {
-            int rc = cdna4_launch_moe_plan(ids, ids_tok_stride, (int)n_tok, (int)n_used, (int)n_b, (int)n_expert, (int)mv.img_rows, mv.img_src, mv.img_dst, mv.tile_expert, (hipStream_t)stream);
-            if (rc) return rc;
-            // few rows per expert (on average at most 32): the int8 matrix-core kernel over 32-row chunks of the same expert-sorted image — the CPU's own integer
-            // block dots (ggml_compute_forward_mul_mat_id's vec_dot calls, ggml-cpu.c:7752-7776) instead of fp16 tiles that would be mostly padding.  The int8
-            // image (quants, d, bsums) takes the place of the fp16 one in the workspace.  Where it wins (MI355X, one box, 8 experts x 2 used x 4096^2, us per call at
-            // 32 / 64 / 128 tokens, profiles/r04/moe64_ab.txt): Q6_K 95 / 96 / 125 vs 158 / 158 / 160 and Q8_0 91 / 92 / 133 vs 144 / 144 / 147 on the grouped per-lane-load
-            // GEMM these formats have; NOT Q4_K, whose grouped k_gemm_kq_t64 takes 45 / 46 / 51 against 82 / 83 / 115 (CDNA4_MMQ_IDS=2 forces it there: 2e-7 from the
-            // oracle instead of 3e-4).  CDNA4_NO_MMQ_IDS=1 turns the route off.
-            static const bool no_mmq_ids = getenv("CDNA4_NO_MMQ_IDS") && atoi(getenv("CDNA4_NO_MMQ_IDS")) != 0;
-            static const bool all_mmq_ids = getenv("CDNA4_MMQ_IDS") && atoi(getenv("CDNA4_MMQ_IDS")) == 2;
-            if (!no_mmq_ids && (type != CDNA4_Q4_K || all_mmq_ids) && n_tok * n_used <= 32 * n_expert && cdna4_mmq_ids_supported(type, K) &&
-                !(((uintptr_t)as | (uintptr_t)w_row_bytes | (uintptr_t)w_expert_bytes) & (type == CDNA4_Q6_K ? 1 : 15))) {
-                ws_view iv{};                                                // the int8 image: [qs][d][bsums (K-quants)]
-                iv.qs = (int8_t *)mv.xh;
-                iv.d = (float *)((uint8_t *)mv.xh + align256((size_t)mv.img_rows * K));
-                int16_t *ibs = (int16_t *)((uint8_t *)iv.d + align256((size_t)mv.img_rows * (K / 32) * 4));
-                rc = cdna4_type_is_kq(type) ? cdna4_launch_quantize_q8_K_gather_i8(b, b_row_stride, K, mv.img_rows, mv.img_src, iv.qs, iv.d, ibs, (hipStream_t)stream)
-                                 : cdna4_launch_quantize_q8_0_gather_i8(b, b_row_stride, K, mv.img_rows, mv.img_src, iv.qs, iv.d, (hipStream_t)stream);
-                if (rc) return rc;
-                iv.bsums = cdna4_type_is_kq(type) ? ibs : nullptr;
-                const cdna4_gemv_args g = gemv_args_of(type, as, w_row_bytes, iv, dst, dst_row_stride, M, K, mv.img_rows, cdna4_epilogue{});
-                return cdna4_launch_mmq_ids(g, mv.tile_expert, mv.img_dst, w_expert_bytes, (hipStream_t)stream);
-            }
-            rc = cdna4_type_is_kq(type) ? cdna4_launch_quantize_q8_K_gather(b, b_row_stride, K, mv.img_rows, mv.img_src, mv.xh, (hipStream_t)stream)
-                             : cdna4_launch_quantize_q8_0_gather(b, b_row_stride, K, mv.img_rows, mv.img_src, mv.xh, (hipStream_t)stream);
-            if (rc) return rc;
-            cdna4_gemm_args a = gemm_args_of(type, as, w_row_bytes, mv.xh, dst, dst_row_stride, M, K, mv.img_rows, 0, 0, cdna4_epilogue{});
-            // Q4_0 experts with a RESIDENT Q4_0R image of the whole stack: Q4_K's grouped kernel instead of the per-lane-load one (round 5)
-            if (const uint8_t *img = moe_q4_0r_image(type, as, w_row_bytes, w_expert_bytes, M, K, n_expert)) {
-                a.type = CDNA4_Q4_0R; a.W = img; a.w_row_bytes = (K / 256) * 144;
-                return cdna4_launch_gemm_t64_ids(a, mv.tile_expert, mv.img_dst, M * a.w_row_bytes, (hipStream_t)stream);
-            }
-            return cdna4_launch_gemm_ids(a, mv.tile_expert, mv.img_dst, w_expert_bytes, (hipStream_t)stream);   // Q4_K: k_gemm_kq_t64<.., IDS>; Q5_K / Q6_K / Q4_0 / Q8_0: k_gemm_q<.., IDS>
-        }
-    }
-    // the MUL_MAT_ID columns of a GEMV launch: column c = (token, slot)
-    const auto gemv_ids = [&](cdna4_gemv_args g) {
-        g.ids = ids; g.ids_tok_stride = ids_tok_stride; g.w_expert_bytes = w_expert_bytes; g.n_used = (int)n_used; g.n_b = (int)n_b; g.n_expert = (int)n_expert;
-        return g;
-    };
-    if (n_tok == 1 && n_used <= 65535 && cdna4_gemv_fused_supported(type, K, 1) && !(((uintptr_t)b | (uintptr_t)(b_row_stride * 4)) & 15)) {
-        // single-token decode of a mixture-of-experts layer: one launch, the activation quantizer runs inside the GEMV
-        const cdna4_gemv_args g = gemv_ids(gemv_args_of(type, as, w_row_bytes, ws_view{}, dst, dst_row_stride, M, K, n_used, cdna4_epilogue{}));
-        return cdna4_launch_gemv_q_fused_ids(g, b, b_row_stride, (hipStream_t)stream);
-    }
-    if (!workspace || ((uintptr_t)workspace & 255)) return cdna4_set_error_msg("mul_mat_id: workspace must be 256-byte aligned");
-    const ws_view v = carve(type, K, nact, workspace);
-    if (workspace_bytes < v.total) return cdna4_set_error_msg("mul_mat_id: workspace too small");
-    const int rc = ggml_cdna4_prepare_act(type, b, b_row_stride, K, nact, workspace, workspace_bytes, GGML_CDNA4_PATH_GEMV, stream);
-    if (rc) return rc;
-    return cdna4_launch_gemv_q(gemv_ids(gemv_args_of(type, as, w_row_bytes, v, dst, dst_row_stride, M, K, n_tok * n_used, cdna4_epilogue{})), (hipStream_t)stream);
+    const mmid_call c = {type, as, w_row_bytes, w_expert_bytes, b, b_row_stride, b_tok_stride, ids, ids_tok_stride, dst, dst_row_stride, dst_tok_stride, M, K, n_expert, n_used, n_b, n_tok, workspace, workspace_bytes};
+    // (no front: answered in front of the fault status, like the key itself)
+    if (!ggml_cdna4_mul_mat_id_front_key(type, as, w_row_bytes, w_expert_bytes, M, K, n_expert, n_used, n_b, n_tok, workspace_bytes)) { cdna4_set_error_msg(mmid_no_front); return -2; }
+    return mul_mat_id_impl(c, true, stream);
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@
 //    k_repack_*      16-byte-aligned re-layout of Q4_0 / Q8_0 / Q6_K into scratch (shallow-K fallback of the staged path)
 #include "gemm_q_common.h"
 #include "gemm_q_plan.hpp"
+#include "mul_mat_id_plan.hpp"
 #include "cdna4_formats.hpp"
 #include <atomic>
 #include <mutex>
@@ -680,7 +681,7 @@ static void plan_type(const cdna4_gemm_args &a, bool registered, gemm_q_plan &pl
 
 
 // grouped MUL_MAT_ID for Q5_K / Q6_K / Q4_0 / Q8_0: one launch of k_gemm_q<.., IDS> over (m tile) x (128-row activation tile of the expert-sorted
-// image); a.B = image rows (a multiple of 128), a.Y rows indexed through row_dst.  (Q4_K: cdna4_launch_gemm_t64_ids.)
+// image); a.B = image rows (a multiple of 128), a.Y rows indexed through row_dst.  (Which calls come here and which go to cdna4_launch_gemm_t64_ids: capi.hip, mmid_make_plan.)
 template <int TYPE>
 static int launch_ids(const cdna4_gemm_args &a, const int32_t *tile_expert, const int32_t *row_dst, int64_t w_expert_bytes, hipStream_t st) {
     gemm_params p{};
@@ -688,13 +689,15 @@ static int launch_ids(const cdna4_gemm_args &a, const int32_t *tile_expert, cons
     p.Y = a.Y; p.y_row = a.y_row_elems; p.M = a.M; p.K = a.K; p.B = a.B; p.splitk = 1;
     p.tiles_m = (a.M + 127) / 128; p.tiles_b = a.B / 128;
     p.tile_expert = tile_expert; p.row_dst = row_dst; p.w_expert_bytes = w_expert_bytes;
-    constexpr bool CAN_LDS = QT<TYPE>::KQ && (QT<TYPE>::BYTES % 16 == 0);
-    const bool wlds = CAN_LDS && ((((uintptr_t)a.W | (uintptr_t)a.w_row_bytes | (uintptr_t)w_expert_bytes) & 15) == 0);
     const dim3 grid(p.tiles_m * p.tiles_b);
-    if constexpr (CAN_LDS) { if (wlds) { hipLaunchKernelGGL((k_gemm_q<TYPE, 4, true, true>), grid, dim3(256), 0, st, p); CDNA4_CHECK_LAUNCH(); return 0; } }
+    if constexpr (QT<TYPE>::KQ && (QT<TYPE>::BYTES % 16 == 0)) { if (cdna4_gemm_ids_wlds(TYPE, a.W, a.w_row_bytes, w_expert_bytes)) { hipLaunchKernelGGL((k_gemm_q<TYPE, 4, true, true>), grid, dim3(256), 0, st, p); CDNA4_CHECK_LAUNCH(); return 0; } }
     hipLaunchKernelGGL((k_gemm_q<TYPE, 4, false, true>), grid, dim3(256), 0, st, p);
     CDNA4_CHECK_LAUNCH();
     return 0;
+}
+// the expert matrices go through LDS: K-quants with whole 16-byte superblocks (Q4_K, Q5_K), 16-byte aligned
+bool cdna4_gemm_ids_wlds(int type, const void *W, int64_t w_row_bytes, int64_t w_expert_bytes) {
+    return cdna4_type_is_kq(type) && cdna4_type_bytes(type) % 16 == 0 && !(((uintptr_t)W | (uintptr_t)w_row_bytes | (uintptr_t)w_expert_bytes) & 15);
 }
 bool cdna4_gemm_ids_supported(int type, int64_t K) {
     const int64_t unit = cdna4_type_is_kq(type) ? 256 : 128;                              // (32-weight formats: whole 128-k panels of the image, whole 64-k slices)
@@ -703,7 +706,6 @@ bool cdna4_gemm_ids_supported(int type, int64_t K) {
 int cdna4_launch_gemm_ids(const cdna4_gemm_args &a, const int32_t *tile_expert, const int32_t *row_dst, int64_t w_expert_bytes, hipStream_t st) {
     if (!cdna4_gemm_ids_supported(a.type, a.K) || a.B % 128) return cdna4_set_error_msg("gemm_ids: unsupported type / K, or image rows not a multiple of 128");
     if (((uintptr_t)a.xh & 15) || (((uintptr_t)a.W | (uintptr_t)a.w_row_bytes | (uintptr_t)w_expert_bytes) & 1)) return cdna4_set_error_msg("gemm_ids: misaligned operands");
-    if (a.type == CDNA4_Q4_K && !(((uintptr_t)a.W | (uintptr_t)a.w_row_bytes | (uintptr_t)w_expert_bytes) & 15)) return cdna4_launch_gemm_t64_ids(a, tile_expert, row_dst, w_expert_bytes, st);
     int rc = 0;
     if (cdna4_dispatch(cdna4_main5{}, a.type, [&](auto t) { rc = launch_ids<t.value>(a, tile_expert, row_dst, w_expert_bytes, st); })) return rc;
     return cdna4_set_error_msg("gemm_ids: unsupported weight type");

@@ -3,6 +3,7 @@
 // (/root/reference/src/ggml-cpu/ggml-cpu.c:7510-7605).
 #include "gemm_q_common.h"
 #include "gemm_q_plan.hpp"
+#include "mul_mat_id_plan.hpp"
 #include "cdna4_formats.hpp"
 #include <stdlib.h>
 #include "gemm_q_hw.h"
@@ -148,50 +149,55 @@ const char *t64_make_plan(const cdna4_gemm_args &a, int tm, int splitk, t64_plan
     return nullptr;
 }
 
-// grouped MUL_MAT_ID: one launch over (m tile) x (activation tile of the expert-sorted image); tiles past the last expert's run exit
-int cdna4_launch_gemm_t64_ids(const cdna4_gemm_args &a, const int32_t *tile_expert, const int32_t *row_dst, int64_t w_expert_bytes, hipStream_t st) {
-    // (Q4_0R: the expert stack's resident re-layout of Q4_0 — capi.hip finds it by the stack's pointer; the same loop with {d_j, 0} constants)
-    if ((a.type != CDNA4_Q4_K && a.type != CDNA4_Q4_0R) || a.K % 256 || a.K < 256 || a.B % 128) return cdna4_set_error_msg("gemm_t64_ids: Q4_K (or Q4_0R), whole superblocks, image rows a multiple of 128");
-    const bool z40 = a.type == CDNA4_Q4_0R;
-    if ((((uintptr_t)a.W | (uintptr_t)a.w_row_bytes | (uintptr_t)w_expert_bytes) & 15) || ((uintptr_t)a.xh & 15)) return cdna4_set_error_msg("gemm_t64_ids: 16-byte alignment of the expert matrices and the image");
-    gemm_params p{};
-    p.W = a.W; p.w_row_bytes = a.w_row_bytes; p.xh = (const half_t *)a.xh; p.xh_row = a.xh_row_elems;
-    p.Y = a.Y; p.y_row = a.y_row_elems; p.M = a.M; p.K = a.K; p.B = a.B; p.splitk = 1;
+// grouped MUL_MAT_ID: tile rows, tables and the wanted split of the launch below (mul_mat_id_plan.hpp).  Side-effect free.
+t64_ids_plan t64_ids_make_plan(int M, int K, int img_rows) {
     // 256-row tiles (no K ways, half the activation bytes per MFMA: 9-12 % at one tile per CU, above) once the grouped grid offers at least 3/4 of a tile per CU;
     // CDNA4_MOE_TM = 128 / 256 forces the form.  8 experts x 2 used x 512 tokens x 4096^2, one box, two alternations: 83.9-84.1 us on 128-row tiles, 74.1-74.2 on 256-row
     // tiles (profiles/r04/moe_tm_ab.txt)
     static const int tm_env = getenv("CDNA4_MOE_TM") ? atoi(getenv("CDNA4_MOE_TM")) : 0;
-    const int cus0 = cdna4_gemm_cu_count();
     // Round 5: the plan also writes a tile ORDER (fullest image tiles first) and per-tile fragment counts (k_moe_plan): the 128-row form starts its tiles in that order and
     // issues no MFMAs for the empty 32-row fragments of an expert's last tile.  Measured at 8 x 2 x 512 x 4096^2, one box, us per call (profiles/r05/moe_ab.txt): 128-row tiles
     // 93.5-94.2 without the tables, 92.3-92.7 with them — and 84.0 on 256-row tiles, which stay the choice there: a full-K 128 x 128 tile takes ~40 us (not the 27 us of the
     // headline's half-K tiles), so the eight full tiles x 32 m-tiles are one 40-us round and the light tiles a second of ~30; the 256-row form is ONE round.  The tables
     // therefore serve the grids that take 128-row tiles by the rule below (CDNA4_MOE_PLAN=0: without them).
     static const bool plan_off = getenv("CDNA4_MOE_PLAN") && atoi(getenv("CDNA4_MOE_PLAN")) == 0;
-    const int tm = tm_env == 128 || tm_env == 256 ? tm_env : ((((a.M + 255) / 256) * (a.B / 128)) * 4 >= cus0 * 3 ? 256 : 128);
-    p.tiles_m = (a.M + tm - 1) / tm; p.tiles_b = a.B / 128;
-    p.tile_expert = tile_expert; p.row_dst = row_dst; p.w_expert_bytes = w_expert_bytes;
-    if (!plan_off && tm == 128) { p.tile_order = tile_expert + p.tiles_b; p.tile_nfrag = tile_expert + 2 * p.tiles_b; }      // (k_moe_plan wrote them behind tile_expert: capi.hip moe_carve)
-    if (tm == 256) {
-        if (z40) hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_0R, 256, true>), dim3(p.tiles_m * p.tiles_b), dim3(512), 0, st, p);
-        else hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_K, 256, true>), dim3(p.tiles_m * p.tiles_b), dim3(512), 0, st, p);
-        CDNA4_CHECK_LAUNCH();
-        return 0;
-    }
     // K split in two with the TICKETED sum (the last of a tile's two work-groups to arrive adds both partial tiles, in the order ks = 0, 1, and stores):
     // OPT-IN (CDNA4_MOE_SPLITK=2) — a measured loss: the grouped grid is 384 30-us tiles on 256 CUs (two rounds) and 768 halves would be three rounds of half
     // the length, but every half tile also parks 64 KB write-through and the last arrival reads its partner's: 8 x 2 x 512 x 4096^2 on one MI355X box,
     // 82.0 us unsplit vs 96.4 us split (gpurun_out/s11, profiles/r04/moe_ab.txt).
     static const int sk_env = getenv("CDNA4_MOE_SPLITK") ? atoi(getenv("CDNA4_MOE_SPLITK")) : 1;
-    const int ntiles = p.tiles_m * p.tiles_b, cus = cdna4_gemm_cu_count();
-    if (sk_env == 2 && a.K / 256 >= 4 && ntiles * 2 > cus && (size_t)ntiles * 8 <= 32768) {
-        p.tile_order = nullptr; p.tile_nfrag = nullptr;                  // (the split's (tile, ks) mapping is the table-free one)
-        const size_t pbytes = (size_t)ntiles * 2 * 8 * 16384, fbytes = 65536;
+    const int cus = cdna4_gemm_cu_count(), tiles_b = img_rows / 128;
+    t64_ids_plan pl;
+    pl.tm = tm_env == 128 || tm_env == 256 ? tm_env : ((((M + 255) / 256) * tiles_b) * 4 >= cus * 3 ? 256 : 128);
+    const int ntiles = ((M + pl.tm - 1) / pl.tm) * tiles_b;
+    pl.splitk = pl.tm == 128 && sk_env == 2 && K / 256 >= 4 && ntiles * 2 > cus && (size_t)ntiles * 8 <= 32768 ? 2 : 1;
+    pl.tables = !plan_off && pl.tm == 128 && pl.splitk == 1;            // (the split's (tile, ks) mapping is the table-free one)
+    return pl;
+}
+// one launch over (m tile) x (activation tile of the expert-sorted image); tiles past the last expert's run exit
+int cdna4_launch_gemm_t64_ids(const cdna4_gemm_args &a, const int32_t *tile_expert, const int32_t *row_dst, int64_t w_expert_bytes, hipStream_t st) {
+    // (Q4_0R: the expert stack's resident re-layout of Q4_0 — capi.hip finds it by the stack's pointer; the same loop with {d_j, 0} constants)
+    if ((a.type != CDNA4_Q4_K && a.type != CDNA4_Q4_0R) || a.K % 256 || a.K < 256 || a.B % 128) return cdna4_set_error_msg("gemm_t64_ids: Q4_K (or Q4_0R), whole superblocks, image rows a multiple of 128");
+    if ((((uintptr_t)a.W | (uintptr_t)a.w_row_bytes | (uintptr_t)w_expert_bytes) & 15) || ((uintptr_t)a.xh & 15)) return cdna4_set_error_msg("gemm_t64_ids: 16-byte alignment of the expert matrices and the image");
+    const t64_ids_plan pl = t64_ids_make_plan(a.M, a.K, a.B);
+    gemm_params p{};
+    p.W = a.W; p.w_row_bytes = a.w_row_bytes; p.xh = (const half_t *)a.xh; p.xh_row = a.xh_row_elems;
+    p.Y = a.Y; p.y_row = a.y_row_elems; p.M = a.M; p.K = a.K; p.B = a.B; p.splitk = 1;
+    p.tiles_m = (a.M + pl.tm - 1) / pl.tm; p.tiles_b = a.B / 128;
+    p.tile_expert = tile_expert; p.row_dst = row_dst; p.w_expert_bytes = w_expert_bytes;
+    if (pl.tables) { p.tile_order = tile_expert + p.tiles_b; p.tile_nfrag = tile_expert + 2 * p.tiles_b; }      // (k_moe_plan wrote them behind tile_expert: capi.hip moe_carve)
+    if (pl.splitk == 2) {                                                // wanted; got only with the scratch (otherwise the unsplit launch)
+        const size_t pbytes = (size_t)p.tiles_m * p.tiles_b * 2 * 8 * 16384, fbytes = 65536;
         char *sc = (char *)cdna4_gemm_scratch(fbytes + pbytes, 2);
         if (sc) { p.splitk = 2; p.tune = 2; p.flags = (unsigned *)sc; p.partial = (float *)(sc + fbytes); }
     }
-    if (z40) hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_0R, 128, true>), dim3(p.tiles_m * p.tiles_b * p.splitk), dim3(512), 0, st, p);
-    else hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_K, 128, true>), dim3(p.tiles_m * p.tiles_b * p.splitk), dim3(512), 0, st, p);
+    const dim3 grid(p.tiles_m * p.tiles_b * p.splitk);
+    const bool z40 = a.type == CDNA4_Q4_0R;
+    if (pl.tm == 256) {
+        if (z40) hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_0R, 256, true>), grid, dim3(512), 0, st, p);
+        else hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_K, 256, true>), grid, dim3(512), 0, st, p);
+    } else if (z40) hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_0R, 128, true>), grid, dim3(512), 0, st, p);
+    else hipLaunchKernelGGL((k_gemm_kq_t64<CDNA4_Q4_K, 128, true>), grid, dim3(512), 0, st, p);
     CDNA4_CHECK_LAUNCH();
     return 0;
 }

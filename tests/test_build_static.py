@@ -751,6 +751,186 @@ def test_prefill_gemm_routing_plan_properties(cus, env):
     assert any(s[2] for s in seen) == owned and any(s[3] for s in seen) == owned, seen      # (the grid reaches the one-launch step and the waiting splits where they may exist)
 
 
+# MUL_MAT_ID routing plans (mul_mat_id_plan.hpp's mmid_make_plan through `lib_emul plan_id`).  Call: "type M K n_expert n_used n_b n_tok as_offset b_offset ws_offset ws_bytes image
+# prepared [dst_gap b_gap]" (type: the ggml type id; the offsets: of the expert stack, b and the workspace from aligned bases; ws_bytes 0: the public workspace size; image: a resident
+# image of the stack is registered; prepared: the `prepared` twin is called; the gaps: elements between the tokens of dst / b), under a CU count and routing knobs.  The expected
+# values are what the calls did BEFORE they had a plan: recorded from the launches of the library in which mul_mat_id_impl, the front key and the grouped launchers each decided for
+# themselves, with the launch calls replaced by prints (kernel instantiation, grid, the parameter structs: where W points, row and expert strides, image rows, the work queue's spans,
+# units, capacity and cost weights, tile rows, tile tables, split, weights through LDS), from that library's return codes, messages and public front key, and `need` as the smallest
+# workspace at which that library's launches are those of the full-size call — not taken from mmid_make_plan.  (A refusal or an empty call names nothing but its return code.)
+MMID_PLAN_TABLE = [
+    (256, {}, "12 130 256 4 2 1 16 0 0 0 0 0 0", "kind=gemv rc=0 wtype=12 w=as+0 wrow=144 wexp=18720 need=45824 rows=16 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {}, "12 130 256 4 2 1 17 0 0 0 0 0 0", "kind=queue rc=0 wtype=12 w=as+0 wrow=144 wexp=18720 need=51200 rows=17 G=256 upt=2 cap=5 cw=10,10,10,10 front=1 tm=0 tables=0 split=0 wlds=0 key=1297154049", 0, ""),
+    (256, {}, "12 4096 4096 8 2 1 512 0 0 0 0 0 0", "kind=queue rc=0 wtype=12 w=as+0 wrow=2304 wexp=9437184 need=4249344 rows=512 G=256 upt=512 cap=17 cw=10,10,10,10 front=1 tm=0 tables=0 split=0 wlds=0 key=1297154049", 0, ""),
+    (8, {}, "12 4096 4096 8 2 1 512 0 0 0 0 0 0", "kind=queue rc=0 wtype=12 w=as+0 wrow=2304 wexp=9437184 need=4249344 rows=512 G=8 upt=512 cap=17 cw=10,10,10,10 front=1 tm=0 tables=0 split=0 wlds=0 key=1297154049", 0, ""),
+    (256, {}, "12 130 256 1024 2 1 17 0 0 0 0 0 0", "kind=queue rc=0 wtype=12 w=as+0 wrow=144 wexp=18720 need=82432 rows=17 G=256 upt=2 cap=35 cw=10,10,10,10 front=1 tm=0 tables=0 split=0 wlds=0 key=1297154049", 0, ""),
+    (256, {}, "12 130 256 1025 2 1 17 0 0 0 0 0 0", "kind=gemv rc=0 wtype=12 w=as+0 wrow=144 wexp=18720 need=46848 rows=17 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {}, "12 130 256 4 2 1 17 2 0 0 0 0 0", "kind=tiles_kq rc=0 wtype=12 w=as+2 wrow=144 wexp=18720 need=365824 rows=640 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {}, "12 130 256 8 2 1 131072 0 0 0 0 0 0", "kind=tiles_t64 rc=0 wtype=12 w=as+0 wrow=144 wexp=18720 need=136904960 rows=263168 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=256 tables=0 split=1 wlds=0 key=0", 0, ""),
+    (256, {}, "14 130 256 4 2 1 17 0 0 0 0 0 0", "kind=tiles_mmq rc=0 wtype=14 w=as+0 wrow=210 wexp=27300 need=365824 rows=640 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {}, "8 130 256 4 2 1 17 0 0 0 0 0 0", "kind=tiles_mmq rc=0 wtype=8 w=as+0 wrow=272 wexp=35360 need=365824 rows=640 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {}, "14 130 256 1 1 1 33 0 0 0 0 0 0", "kind=tiles_kq rc=0 wtype=14 w=as+0 wrow=210 wexp=27300 need=166144 rows=256 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {}, "14 130 256 2 1 1 33 0 0 0 0 0 0", "kind=tiles_mmq rc=0 wtype=14 w=as+0 wrow=210 wexp=27300 need=232704 rows=384 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {}, "13 130 256 1 1 1 33 0 0 0 0 0 0", "kind=tiles_kq rc=0 wtype=13 w=as+0 wrow=176 wexp=22880 need=166144 rows=256 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=1 key=0", 0, ""),
+    (256, {}, "13 130 256 1 1 1 33 2 0 0 0 0 0", "kind=tiles_kq rc=0 wtype=13 w=as+2 wrow=176 wexp=22880 need=166144 rows=256 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {}, "13 130 256 4 2 1 17 2 0 0 0 0 0", "kind=tiles_kq rc=0 wtype=13 w=as+2 wrow=176 wexp=22880 need=365824 rows=640 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {}, "2 130 256 4 2 1 17 0 0 0 0 1 0", "kind=queue rc=0 wtype=102 w=img+0 wrow=144 wexp=18720 need=51200 rows=17 G=256 upt=2 cap=5 cw=10,10,10,10 front=1 tm=0 tables=0 split=0 wlds=0 key=1297154050", 0, ""),
+    (256, {}, "2 130 256 4 2 1 17 0 0 0 0 0 0", "kind=tiles_mmq rc=0 wtype=2 w=as+0 wrow=144 wexp=18720 need=365824 rows=640 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {}, "2 130 256 1 1 1 33 0 0 0 0 0 0", "kind=tiles_kq rc=0 wtype=2 w=as+0 wrow=144 wexp=18720 need=166144 rows=256 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {}, "2 130 320 4 2 1 17 0 0 0 0 1 0", "kind=gemv rc=0 wtype=2 w=as+0 wrow=180 wexp=23400 need=52992 rows=17 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {"CDNA4_MOE_SK": "0"}, "2 130 256 1 1 1 33 0 0 0 0 1 0", "kind=tiles_t64 rc=0 wtype=102 w=img+0 wrow=144 wexp=18720 need=166144 rows=256 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=128 tables=1 split=1 wlds=0 key=0", 0, ""),
+    (256, {"CDNA4_MOE_SK": "0"}, "2 130 256 4 2 1 17 0 0 0 0 1 0", "kind=tiles_mmq rc=0 wtype=2 w=as+0 wrow=144 wexp=18720 need=365824 rows=640 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {}, "12 130 256 4 2 1 17 0 0 0 51199 0 0", "kind=gemv rc=0 wtype=12 w=as+0 wrow=144 wexp=18720 need=46848 rows=17 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {}, "14 130 256 1 1 1 33 0 0 0 166143 0 0", "kind=gemv rc=0 wtype=14 w=as+0 wrow=210 wexp=27300 need=59648 rows=33 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {}, "14 130 256 1 1 1 33 0 0 0 1000 0 0", "kind=refused rc=-1 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -1, "mul_mat_id: workspace too small"),
+    (256, {}, "14 130 32768 8 1 1 32767 0 0 0 0 0 0", "kind=gemv rc=0 wtype=14 w=as+0 wrow=26880 wexp=3494400 need=3372150272 rows=32767 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {}, "12 4096 4096 8 2 1 1 0 0 0 0 0 0", "kind=gemv_1 rc=0 wtype=12 w=as+0 wrow=2304 wexp=9437184 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {}, "12 4096 4096 8 2 1 1 0 4 0 0 0 0", "kind=refused rc=-1 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -1, "quantize_q8_K: x must be 16-byte aligned"),
+    (256, {}, "3 130 256 4 2 2 1 0 0 0 0 0 0", "kind=gemv_1 rc=0 wtype=3 w=as+0 wrow=160 wexp=20800 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {}, "8 130 544 4 2 1 1 0 0 0 0 0 0", "kind=gemv rc=0 wtype=8 w=as+0 wrow=578 wexp=75140 need=35328 rows=1 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {"CDNA4_MOE_SK": "0"}, "12 4096 4096 8 2 1 512 0 0 0 0 0 0", "kind=tiles_t64 rc=0 wtype=12 w=as+0 wrow=2304 wexp=9437184 need=16826624 rows=2048 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=256 tables=0 split=1 wlds=0 key=0", 0, ""),
+    (8, {"CDNA4_MOE_SK": "0"}, "12 4096 4096 8 2 1 512 0 0 0 0 0 0", "kind=tiles_t64 rc=0 wtype=12 w=as+0 wrow=2304 wexp=9437184 need=16826624 rows=2048 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=256 tables=0 split=1 wlds=0 key=0", 0, ""),
+    (256, {"CDNA4_MOE_SK": "0"}, "12 512 1024 4 2 1 17 0 0 0 0 0 0", "kind=tiles_t64 rc=0 wtype=12 w=as+0 wrow=576 wexp=294912 need=1348864 rows=640 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=128 tables=1 split=1 wlds=0 key=0", 0, ""),
+    (8, {"CDNA4_MOE_SK": "0"}, "12 512 1024 4 2 1 17 0 0 0 0 0 0", "kind=tiles_t64 rc=0 wtype=12 w=as+0 wrow=576 wexp=294912 need=1348864 rows=640 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=256 tables=0 split=1 wlds=0 key=0", 0, ""),
+    (256, {"CDNA4_MOE_SK": "0"}, "12 4096 256 8 2 1 320 0 0 0 0 0 0", "kind=tiles_t64 rc=0 wtype=12 w=as+0 wrow=144 wexp=589824 need=898304 rows=1664 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=256 tables=0 split=1 wlds=0 key=0", 0, ""),
+    (256, {"CDNA4_MOE_SK": "0"}, "12 130 256 4 2 1 17 0 0 0 0 0 0", "kind=tiles_t64 rc=0 wtype=12 w=as+0 wrow=144 wexp=18720 need=365824 rows=640 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=128 tables=1 split=1 wlds=0 key=0", 0, ""),
+    (256, {"CDNA4_MOE_SK": "0", "CDNA4_MOE_TM": "128"}, "12 4096 4096 8 2 1 512 0 0 0 0 0 0", "kind=tiles_t64 rc=0 wtype=12 w=as+0 wrow=2304 wexp=9437184 need=16826624 rows=2048 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=128 tables=1 split=1 wlds=0 key=0", 0, ""),
+    (8, {"CDNA4_MOE_SK": "0", "CDNA4_MOE_TM": "256"}, "12 130 1024 4 2 1 17 0 0 0 0 0 0", "kind=tiles_t64 rc=0 wtype=12 w=as+0 wrow=576 wexp=74880 need=1348864 rows=640 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=256 tables=0 split=1 wlds=0 key=0", 0, ""),
+    (256, {"CDNA4_MOE_SK": "0", "CDNA4_MOE_PLAN": "0"}, "12 130 1024 4 2 1 17 0 0 0 0 0 0", "kind=tiles_t64 rc=0 wtype=12 w=as+0 wrow=576 wexp=74880 need=1348864 rows=640 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=128 tables=0 split=1 wlds=0 key=0", 0, ""),
+    (8, {"CDNA4_MOE_SK": "0", "CDNA4_MOE_PLAN": "0"}, "12 130 1024 4 2 1 17 0 0 0 0 0 0", "kind=tiles_t64 rc=0 wtype=12 w=as+0 wrow=576 wexp=74880 need=1348864 rows=640 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=128 tables=0 split=1 wlds=0 key=0", 0, ""),
+    (256, {"CDNA4_MOE_SK": "0", "CDNA4_MOE_SPLITK": "2"}, "12 130 1024 4 2 1 17 0 0 0 0 0 0", "kind=tiles_t64 rc=0 wtype=12 w=as+0 wrow=576 wexp=74880 need=1348864 rows=640 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=128 tables=1 split=1 wlds=0 key=0", 0, ""),
+    (8, {"CDNA4_MOE_SK": "0", "CDNA4_MOE_SPLITK": "2"}, "12 130 1024 4 2 1 17 0 0 0 0 0 0", "kind=tiles_t64 rc=0 wtype=12 w=as+0 wrow=576 wexp=74880 need=1348864 rows=640 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=128 tables=0 split=2 wlds=0 key=0", 0, ""),
+    (256, {"CDNA4_MMQ_IDS": "2"}, "12 130 256 4 2 1 17 0 0 0 0 0 0", "kind=tiles_mmq rc=0 wtype=12 w=as+0 wrow=144 wexp=18720 need=365824 rows=640 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (8, {"CDNA4_MMQ_IDS": "2"}, "12 130 256 4 2 1 17 0 0 0 0 0 0", "kind=tiles_mmq rc=0 wtype=12 w=as+0 wrow=144 wexp=18720 need=365824 rows=640 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {"CDNA4_MMQ_IDS": "2"}, "12 130 256 1 1 1 33 0 0 0 0 0 0", "kind=queue rc=0 wtype=12 w=as+0 wrow=144 wexp=18720 need=56320 rows=33 G=256 upt=2 cap=2 cw=10,10,10,10 front=1 tm=0 tables=0 split=0 wlds=0 key=1297154049", 0, ""),
+    (256, {"CDNA4_NO_MMQ_IDS": "1"}, "14 130 256 4 2 1 17 0 0 0 0 0 0", "kind=tiles_kq rc=0 wtype=14 w=as+0 wrow=210 wexp=27300 need=365824 rows=640 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (8, {"CDNA4_NO_MMQ_IDS": "1"}, "8 130 256 4 2 1 17 0 0 0 0 0 0", "kind=tiles_kq rc=0 wtype=8 w=as+0 wrow=272 wexp=35360 need=365824 rows=640 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {"CDNA4_SK_CW": "4,6,8,10"}, "12 130 256 4 2 1 17 0 0 0 0 0 0", "kind=queue rc=0 wtype=12 w=as+0 wrow=144 wexp=18720 need=51200 rows=17 G=256 upt=2 cap=5 cw=4,6,8,10 front=1 tm=0 tables=0 split=0 wlds=0 key=1297154049", 0, ""),
+    (8, {"CDNA4_SK_CW": "4,6,8,10"}, "12 130 256 4 2 1 17 0 0 0 0 0 0", "kind=queue rc=0 wtype=12 w=as+0 wrow=144 wexp=18720 need=51200 rows=17 G=8 upt=2 cap=5 cw=4,6,8,10 front=1 tm=0 tables=0 split=0 wlds=0 key=1297154049", 0, ""),
+    (256, {"CDNA4_SK_SPANS": "40"}, "12 130 256 4 2 1 17 0 0 0 0 0 0", "kind=queue rc=0 wtype=12 w=as+0 wrow=144 wexp=18720 need=51200 rows=17 G=40 upt=2 cap=5 cw=10,10,10,10 front=1 tm=0 tables=0 split=0 wlds=0 key=1297154049", 0, ""),
+    (8, {"CDNA4_SK_SPANS": "40"}, "12 130 256 4 2 1 17 0 0 0 0 0 0", "kind=queue rc=0 wtype=12 w=as+0 wrow=144 wexp=18720 need=51200 rows=17 G=40 upt=2 cap=5 cw=10,10,10,10 front=1 tm=0 tables=0 split=0 wlds=0 key=1297154049", 0, ""),
+    (8, {}, "12 130 256 4 2 1 17 0 0 0 0 0 0", "kind=queue rc=0 wtype=12 w=as+0 wrow=144 wexp=18720 need=51200 rows=17 G=8 upt=2 cap=5 cw=10,10,10,10 front=1 tm=0 tables=0 split=0 wlds=0 key=1297154049", 0, ""),
+    (256, {}, "12 130 256 4 2 1 17 0 0 0 0 0 1", "kind=queue rc=0 wtype=12 w=as+0 wrow=144 wexp=18720 need=51200 rows=17 G=256 upt=2 cap=5 cw=10,10,10,10 front=2 tm=0 tables=0 split=0 wlds=0 key=1297154049", 0, ""),
+    (256, {}, "2 130 256 4 2 1 17 0 0 0 0 1 1", "kind=queue rc=0 wtype=102 w=img+0 wrow=144 wexp=18720 need=51200 rows=17 G=256 upt=2 cap=5 cw=10,10,10,10 front=2 tm=0 tables=0 split=0 wlds=0 key=1297154050", 0, ""),
+    (256, {}, "14 130 256 4 2 1 17 0 0 0 0 0 1", "kind=refused rc=-2 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -2, "mul_mat_id_prepared: a call of this shape leaves no front (ggml_cdna4_mul_mat_id_front_key == 0)"),
+    (256, {}, "12 130 256 4 2 1 17 0 4 0 0 0 1", "kind=refused rc=-2 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -2, "mul_mat_id_prepared: misaligned operands"),
+    (256, {}, "12 130 256 4 2 1 17 0 0 128 0 0 1", "kind=refused rc=-2 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -2, "mul_mat_id_prepared: misaligned operands"),
+    (256, {"CDNA4_MOE_SK": "0"}, "12 130 256 4 2 1 17 0 0 0 0 0 1", "kind=refused rc=-2 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -2, "mul_mat_id_prepared: a call of this shape leaves no front (ggml_cdna4_mul_mat_id_front_key == 0)"),
+    (256, {}, "0 130 256 4 2 1 17 0 0 0 0 0 0", "kind=refused rc=-1 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -1, "mul_mat_id: unsupported weight type"),
+    (256, {}, "12 0 256 4 2 1 17 0 0 0 0 0 0", "kind=empty rc=0 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", 0, ""),
+    (256, {}, "12 130 100 4 2 1 17 0 0 0 0 0 0", "kind=refused rc=-1 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -1, "mul_mat_id: K is not a whole number of blocks"),
+    (256, {}, "12 130 256 4 3 2 17 0 0 0 0 0 0", "kind=refused rc=-1 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -1, "mul_mat_id: n_used must be a multiple of b.ne[1]"),
+    (256, {}, "12 130 256 4 2 1 17 0 0 0 0 0 0 1 0", "kind=refused rc=-1 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -1, "mul_mat_id: dst must be contiguous over (slot, token)"),
+    (256, {}, "12 130 256 4 2 1 17 0 0 0 0 0 0 0 4", "kind=refused rc=-1 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -1, "mul_mat_id: b must be contiguous over (row, token)"),
+    (256, {}, "12 130 256 4 2 1 16 0 0 128 0 0 0", "kind=refused rc=-1 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -1, "mul_mat_id: workspace must be 256-byte aligned"),
+    (256, {}, "12 130 256 4 2 1 16 0 0 0 1000 0 0", "kind=refused rc=-1 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -1, "mul_mat_id: workspace too small"),
+    (256, {}, "12 130 256 4 2 1 16 0 4 0 0 0 0", "kind=refused rc=-1 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -1, "quantize_q8_K: x must be 16-byte aligned"),
+    (256, {}, "8 130 256 4 2 1 16 0 4 0 0 0 0", "kind=refused rc=-1 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -1, "quantize_q8_0: x must be 16-byte aligned"),
+    (256, {}, "3 130 256 4 2 1 16 0 4 0 0 0 0", "kind=refused rc=-1 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -1, "quantize_q8_1: x must be 16-byte aligned"),
+    (256, {}, "8 130 256 4 2 1 16 1 0 0 0 0 0", "kind=refused rc=-1 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -1, "gemv_q: misaligned operands"),
+    (256, {}, "14 130 4096 8 2 1 131072 0 0 0 0 0 0", "kind=refused rc=-1 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -1, "gemv_q: too many MUL_MAT_ID columns"),
+    (256, {}, "12 130 256 4 2 1 16 2 0 0 0 0 0", "kind=refused rc=-1 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -1, "gemv_q: Q4_K/Q5_K rows must be 16-byte aligned"),
+    (256, {}, "13 130 256 4 2 1 1 2 0 0 0 0 0", "kind=refused rc=-1 wtype=0 w=as+0 wrow=0 wexp=0 need=0 rows=0 G=0 upt=0 cap=0 cw=0,0,0,0 front=0 tm=0 tables=0 split=0 wlds=0 key=0", -1, "gemv_q: Q4_K/Q5_K rows must be 16-byte aligned"),
+]
+
+
+def _mmid_plans_by_setting(rows):
+    """rows (cus, env, call, ..) -> their plans, one `lib_emul plan_id` process per (cus, env)"""
+    mod, out, groups = _emul_module("lib_emul_check"), {}, {}
+    for i, r in enumerate(rows):
+        groups.setdefault((r[0], tuple(sorted(r[1].items()))), []).append(i)
+    for (cus, env), idx in groups.items():
+        for i, p in zip(idx, mod.plan_id([rows[i][2].split() for i in idx], cus=cus, env=dict(env))):
+            out[i] = p
+    return [out[i] for i in range(len(rows))]
+
+
+def test_mul_mat_id_routing_plans_of_a_table_of_calls():
+    """every routing rule of MUL_MAT_ID at a call that takes it, with the plan the call must get (see MMID_PLAN_TABLE): the kind, what the kernel reads, the workspace view's
+    bytes, the work queue's geometry, the grouped k_gemm_kq_t64's tiles / tables / split, k_gemm_q's weights through LDS, the front key; every refusal with its return code and
+    message.  And the call on the same arguments answers what the plan says."""
+    for (cus, env, call, want, want_rc, want_msg), p in zip(MMID_PLAN_TABLE, _mmid_plans_by_setting(MMID_PLAN_TABLE)):
+        assert p["line"] == want and p["pure"] == 1 and (p["call_rc"], p["msg"]) == (want_rc, want_msg), (cus, env, call, p["line"], p["call_rc"], p["msg"])
+
+
+def _mmid_cells():
+    """(type, M, K, n_expert, n_used, n_b, n_tok, as_offset, b_offset, ws_offset, ws_bytes, image, prepared): every accepted type x shapes on both sides of every threshold x
+    operand alignments x workspace sizes x a registered stack image x the `prepared` twin"""
+    cells = []
+    for _, t in LIB_TYPES:
+        for m in (130, 4096):
+            for k in (256, 320, 4096):                                   # (320: whole blocks of the 32-weight formats only, and no whole 128-k panel)
+                for ne, nu, nb in ((1, 1, 1), (4, 2, 1), (8, 2, 2), (1025, 2, 1), (4, 3, 2)):
+                    for nt in (1, 16, 17, 33, 129, 512):
+                        for ao, bo, wo, ws, img in ((0, 0, 0, 0, 0), (2, 0, 0, 0, 0), (1, 0, 0, 0, 0), (0, 4, 0, 0, 0), (0, 0, 128, 0, 0), (0, 0, 0, 65536, 0), (0, 0, 0, 1 << 20, 0),
+                                                    (0, 0, 0, 0, 1), (2, 0, 0, 0, 1)):
+                            if img and t not in (2, 8, 12):
+                                continue
+                            for prep in (0, 1):
+                                if prep and (nt < 17 or ws == 65536 or ao == 1):
+                                    continue
+                                cells.append((t, m, k, ne, nu, nb, nt, ao, bo, wo, ws, img, prep))
+    # an empty call; more tile records than the planner holds (the per-tile launches); an expert-sorted image that 32-bit byte offsets do not reach (GEMV, too many columns)
+    cells += [(12, 0, 256, 4, 2, 1, 17, 0, 0, 0, 0, 0, 0), (12, 130, 256, 4, 2, 1, 0, 0, 0, 0, 0, 0, 0), (12, 130, 256, 8, 2, 1, 131072, 0, 0, 0, 0, 0, 0), (12, 130, 256, 8, 2, 1, 131072, 0, 0, 0, 0, 0, 1),
+              (12, 130, 4096, 8, 2, 1, 131072, 0, 0, 0, 0, 0, 0), (14, 130, 4096, 8, 2, 1, 131072, 0, 0, 0, 0, 0, 0), (2, 130, 256, 8, 2, 1, 131072, 0, 0, 0, 0, 1, 0)]
+    return cells
+
+
+MMID_SETTINGS = [(256, {}), (8, {}), (256, {"CDNA4_MOE_SK": "0"}), (8, {"CDNA4_MOE_SK": "0"}), (256, {"CDNA4_MMQ_IDS": "2"}), (8, {"CDNA4_MMQ_IDS": "2"})]
+
+
+@pytest.mark.parametrize("cus,env", MMID_SETTINGS)
+def test_mul_mat_id_routing_plan_properties(cus, env):
+    """what holds for the plan of ANY MUL_MAT_ID call, over more than twenty thousand cells (_mmid_cells) under the default routing, without the work-queue form and with the int8
+    matrix cores forced: planning is repeatable and leaves the error text alone; the plan refuses exactly the calls the call refuses, with the same return code and message;
+    the public front key is non-zero exactly on the work-queue kind and is the plan's; an aligned `prepared` call succeeds exactly where the key is non-zero; the kernels read a
+    Q4_0R image exactly when one is registered for a Q4_0 stack of whole superblocks (on the fp16 grouped kinds: the integer-dot kinds read the caller's Q4_0 blocks), and the
+    caller's stack otherwise; the bytes a plan made with the public workspace size needs never exceed that size; every kind occurs."""
+    cells = _mmid_cells()
+    assert len(cells) > 20000
+    kinds = set()
+    checked = 0
+    for c, p in zip(cells, _emul_module("lib_emul_check").plan_id(cells, cus=cus, env=env)):
+        t, m, k, ne, nu, nb, nt, ao, bo, wo, ws, img, prep = c
+        why = (c, p["line"], p["call_rc"], p["msg"])
+        assert p["pure"] == 1, why
+        assert (p["kind"] == "refused") == (p["call_rc"] != 0) and p["rc"] == p["call_rc"], why
+        if p["kind"] == "refused":
+            assert p["rc"] in (-1, -2) and p["plan_err"] == 1 and p["key"] == 0, why
+        aligned = not (bo or wo)                                         # (the key is asked with aligned stand-ins for b and the workspace)
+        assert p["key"] == (p["pubkey"] if p["kind"] == "queue" else 0) and (aligned or p["kind"] != "queue"), why
+        if aligned:
+            assert (p["pubkey"] != 0) == (p["kind"] == "queue"), why
+        if prep:
+            assert p["kind"] in ("queue", "refused") and p["rc"] == (0 if p["kind"] == "queue" else -2) and p["front"] == (2 if p["kind"] == "queue" else 0), why
+            assert p["msg"] == ("" if p["kind"] == "queue" else "mul_mat_id_prepared: misaligned operands" if p["pubkey"] else
+                                "mul_mat_id_prepared: a call of this shape leaves no front (ggml_cdna4_mul_mat_id_front_key == 0)"), why
+        else:
+            assert p["front"] == (1 if p["kind"] == "queue" else 0) and p["rc"] in (0, -1), why
+        image = bool(img) and t == 2 and k % 256 == 0
+        if p["kind"] in ("queue", "tiles_t64", "tiles_kq"):
+            assert (p["wtype"], p["w"], p["wrow"], p["wexp"]) == ((102, "img+0", k // 256 * 144, m * (k // 256 * 144)) if image else (t, "as+%d" % ao, p["wrow"], m * p["wrow"])), why
+        elif p["kind"] not in ("refused", "empty"):
+            assert (p["wtype"], p["w"]) == (t, "as+%d" % ao), why
+        if not ws:
+            assert p["msg"] != "mul_mat_id: workspace too small" and (p["kind"] == "refused" or p["need"] <= p["size"]), why
+        if env.get("CDNA4_MOE_SK") == "0":
+            assert p["kind"] != "queue", why
+        kinds.add(p["kind"])
+        checked += 1
+    assert checked == len(cells)
+    want = {"empty", "refused", "tiles_mmq", "tiles_t64", "tiles_kq", "gemv_1", "gemv"} | (set() if env.get("CDNA4_MOE_SK") == "0" else {"queue"})
+    assert kinds == want, kinds
+
+
+def test_each_mul_mat_id_knob_is_read_in_one_place():
+    """CDNA4_MMQ_IDS used to be read twice under two names (in front of the work queue and in front of the int8 route): once now, in the plan's knobs"""
+    text = open(os.path.join(ROOT, "ggml_amd", "csrc", "capi.hip")).read()
+    assert text.count('getenv("CDNA4_MMQ_IDS")') == 1
+    for knob in ("CDNA4_MOE_SK", "CDNA4_NO_MMQ_IDS", "CDNA4_SK_CW"):
+        assert text.count('getenv("%s")' % knob) == 1, knob
+
+
 def test_no_route_probe_is_left_in_the_kernel_library():
     """the armed probe (a thread-local switch that made the launcher return in front of its first side effect) is gone: the queries read the plan"""
     csrc = os.path.join(ROOT, "ggml_amd", "csrc")

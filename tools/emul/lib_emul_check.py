@@ -147,6 +147,25 @@ def plan(calls, cus=256, env=None):
     return out
 
 
+def plan_id(calls, cus=256, env=None):
+    """MUL_MAT_ID's routing plans (mul_mat_id_plan.hpp: mmid_make_plan through `lib_emul plan_id`; no kernel runs).  calls: tuples (type, M, K, n_expert, n_used, n_b, n_tok,
+    as_offset, b_offset, ws_offset, ws_bytes, image, prepared) — see lib_emul_main.cpp; env: routing knobs (CDNA4_MOE_SK, CDNA4_MMQ_IDS, ..).  Returns one dict per call: the
+    plan's fields, `line` (the fields as printed), `pure`, `size` (the public workspace size), `call_rc` / `msg` of the call itself, `plan_err`, `pubkey` (the public front key)"""
+    knobs = ("CDNA4_MOE_SK", "CDNA4_MMQ_IDS", "CDNA4_NO_MMQ_IDS", "CDNA4_SK_CW", "CDNA4_SK_SPANS", "CDNA4_MOE_TM", "CDNA4_MOE_PLAN", "CDNA4_MOE_SPLITK", "EMU_NO_RUN")
+    r = subprocess.run([build(), "plan_id"], input="".join(" ".join(str(int(x)) for x in c) + "\n" for c in calls), capture_output=True, text=True, timeout=600,
+                       env=dict({k: v for k, v in os.environ.items() if k not in knobs}, EMU_CUS=str(cus), **(env or {})))
+    assert r.returncode == 0, (r.returncode, r.stderr[-800:])
+    lines = r.stdout.splitlines()
+    assert len(lines) == len(calls), (len(lines), len(calls))
+    out = []
+    for ln in lines:
+        fields, msg = ln.split(" | ", 1) if " | " in ln else (ln.rstrip(" |"), "")
+        d = {k: (int(v) if v.lstrip("-").isdigit() else v) for k, v in (f.split("=") for f in fields.split())}
+        d["line"] = fields[:fields.index(" pure=")]; d["msg"] = msg
+        out.append(d)
+    return out
+
+
 if __name__ == "__main__":
     a = [int(v) for v in sys.argv[1:]]
     t, m, k, b = a[:4] if len(a) >= 4 else (R.Q4_1, 130, 768, 33)

@@ -2,9 +2,11 @@
 //   lib_emul mul_mat type M K B path w.bin x.bin y.bin          ggml_cdna4_mul_mat (path 0 = auto, 1 = GEMV, 2 = GEMM); w = M contiguous rows, x = [B][K] f32, y = [B][M]
 //   lib_emul mul_mat_id type M K n_expert n_used n_b n_tok w.bin x.bin ids.bin y.bin
 //   lib_emul plan < calls                                      the prefill GEMM's routing plans (gemm_q_plan.hpp), no kernel runs: see below
+//   lib_emul plan_id < calls                                   MUL_MAT_ID's routing plans (mul_mat_id_plan.hpp), likewise
 #include "lib_emul.h"
 #include "../../include/ggml_cdna4.h"
 #include "gemm_q_plan.hpp"
+#include "mul_mat_id_plan.hpp"
 #include <string>
 int cdna4_set_error_msg(const char *msg);
 
@@ -120,6 +122,52 @@ int main(int argc, char **argv) {
         }
         return 0;
     }
-    fprintf(stderr, "usage: lib_emul mul_mat type M K B path w.bin x.bin y.bin | lib_emul mul_mat_id type M K n_expert n_used n_b n_tok w.bin x.bin ids.bin y.bin | lib_emul plan < calls\n");
+    if (argc >= 2 && !strcmp(argv[1], "plan_id")) {
+        // one line per call, "type M K n_expert n_used n_b n_tok as_offset b_offset ws_offset ws_bytes image prepared [dst_gap b_gap]": MUL_MAT_ID's plan (mmid_make_plan) as field=value, made
+        // twice (`pure`), then what the call itself — ggml_cdna4_mul_mat_id, or its `prepared` twin — answers with every launch a no-op: rc, `plan_err` (the plan named the very
+        // message the call failed with), the public front key, and the message behind `|`.  Operands are addresses without memory behind them, contiguous, at the given byte
+        // offsets from aligned bases (the weights as `w=` are printed as an offset from their stack, or from the image); ws_bytes 0: what ggml_cdna4_mul_mat_id_workspace_size
+        // says (printed as `size=`); image != 0: with a resident image of the stack registered; dst_gap / b_gap: elements between the tokens of dst / b
+        setenv("EMU_NO_RUN", "1", 1);
+        const uintptr_t as0 = (uintptr_t)1 << 40, img0 = (uintptr_t)2 << 40, b0 = (uintptr_t)3 << 40, ws0 = (uintptr_t)4 << 40, ids0 = (uintptr_t)5 << 40, dst0 = (uintptr_t)6 << 40;
+        auto line_of = [&](const mmid_plan &made) {
+            mmid_plan pl = made;                                        // (a refusal and an empty call name nothing else)
+            if (made.kind == MMID_REFUSED || made.kind == MMID_EMPTY) { pl = mmid_plan{}; pl.kind = made.kind; pl.rc = made.rc; pl.W = (const uint8_t *)as0; }
+            static const char *kind[] = {"empty", "refused", "queue", "tiles_mmq", "tiles_t64", "tiles_kq", "gemv_1", "gemv"};
+            const bool q = pl.kind == MMID_QUEUE, t = pl.kind == MMID_TILES_T64;
+            const uintptr_t w = (uintptr_t)pl.W;
+            char b[512];
+            snprintf(b, sizeof b, "kind=%s rc=%d wtype=%d w=%s%lld wrow=%lld wexp=%lld need=%zu rows=%lld G=%d upt=%lld cap=%lld cw=%d,%d,%d,%d front=%d tm=%d tables=%d split=%d wlds=%d key=%u",
+                     kind[pl.kind], pl.rc, pl.w_type, w >= img0 ? "img+" : "as+", (long long)(w - (w >= img0 ? img0 : as0)), (long long)pl.w_row_bytes, (long long)pl.w_expert_bytes, pl.ws_need,
+                     (long long)pl.rows, pl.G, (long long)pl.upt, (long long)pl.ntile_cap, pl.cw[0], pl.cw[1], pl.cw[2], pl.cw[3], q ? (pl.front_in_place ? 2 : 1) : 0,
+                     t ? pl.t64.tm : 0, t ? (int)pl.t64.tables : 0, t ? pl.t64.splitk : 0, (int)pl.wlds, pl.front_key);
+            return std::string(b);
+        };
+        char in[256];
+        while (fgets(in, sizeof in, stdin)) {
+            long long v[15] = {0};
+            if (sscanf(in, "%lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld %lld", v, v + 1, v + 2, v + 3, v + 4, v + 5, v + 6, v + 7, v + 8, v + 9, v + 10, v + 11, v + 12, v + 13, v + 14) < 7) continue;
+            mmid_call c{};
+            c.type = (int)v[0]; c.M = v[1]; c.K = v[2]; c.n_expert = v[3]; c.n_used = v[4]; c.n_b = v[5]; c.n_tok = v[6];
+            c.as = (const void *)(as0 + v[7]); c.w_row_bytes = (int64_t)ggml_cdna4_row_size(c.type, c.K); c.w_expert_bytes = c.M * c.w_row_bytes;
+            c.b = (const float *)(b0 + v[8]); c.b_row_stride = c.K; c.b_tok_stride = c.n_b * c.K + v[14];
+            c.ids = (const int32_t *)ids0; c.ids_tok_stride = c.n_used; c.dst = (float *)dst0; c.dst_row_stride = c.M; c.dst_tok_stride = c.n_used * c.M + v[13];
+            const size_t size = ggml_cdna4_mul_mat_id_workspace_size(c.type, c.K, c.n_expert, c.n_used, c.n_b, c.n_tok);
+            c.workspace = (void *)(ws0 + v[9]); c.workspace_bytes = v[10] ? (size_t)v[10] : size;
+            const bool image = v[11] && !cdna4_resident_register(c.type, c.as, c.w_row_bytes, c.M * c.n_expert, c.K, (const void *)img0), prepared = v[12] != 0;
+            cdna4_set_error_msg("untouched");
+            const mmid_plan pl = mmid_make_plan(c, prepared);
+            const std::string l1 = line_of(pl), l2 = line_of(mmid_make_plan(c, prepared));
+            const bool pure = l1 == l2 && !strcmp(ggml_cdna4_last_error(), "untouched");
+            const int rc = (prepared ? ggml_cdna4_mul_mat_id_prepared : ggml_cdna4_mul_mat_id)(c.type, c.as, c.w_row_bytes, c.w_expert_bytes, c.b, c.b_row_stride, c.b_tok_stride, c.ids, c.ids_tok_stride,
+                c.dst, c.dst_row_stride, c.dst_tok_stride, c.M, c.K, c.n_expert, c.n_used, c.n_b, c.n_tok, c.workspace, c.workspace_bytes, nullptr);
+            const std::string msg = rc ? ggml_cdna4_last_error() : "";
+            const uint32_t key = ggml_cdna4_mul_mat_id_front_key(c.type, c.as, c.w_row_bytes, c.w_expert_bytes, c.M, c.K, c.n_expert, c.n_used, c.n_b, c.n_tok, c.workspace_bytes);
+            printf("%s pure=%d size=%zu call_rc=%d plan_err=%d pubkey=%u | %s\n", l1.c_str(), (int)pure, size, rc, (int)(pl.err != nullptr && msg == pl.err), key, msg.c_str());
+            if (image) cdna4_resident_unregister(c.as);
+        }
+        return 0;
+    }
+    fprintf(stderr, "usage: lib_emul mul_mat type M K B path w.bin x.bin y.bin | lib_emul mul_mat_id type M K n_expert n_used n_b n_tok w.bin x.bin ids.bin y.bin | lib_emul plan < calls | lib_emul plan_id < calls\n");
     return 2;
 }
