@@ -711,21 +711,16 @@ int cdna4_launch_to_f16_dense(const T4 *a, void *dst, int64_t dst_row, hipStream
     CDNA4_CHECK_LAUNCH();
     return 0;
 }
-extern "C" {
-
-int ggml_cdna4_op_mul_mat_f(const T4 *a, const T4 *b, const T4 *d, void *stream) {
-    NEED((a->type == CDNA4_F32 || a->type == CDNA4_F16) && b->type == CDNA4_F32 && d->type == CDNA4_F32, "mul_mat_f: F32/F16 x F32 only");
-    NEED(a->ne[0] == b->ne[0] && d->ne[0] == a->ne[1] && d->ne[1] == b->ne[1] && d->ne[2] == b->ne[2] && d->ne[3] == b->ne[3], "mul_mat_f: shape mismatch");
-    NEED(a->ne[2] > 0 && a->ne[3] > 0 && b->ne[2] % a->ne[2] == 0 && b->ne[3] % a->ne[3] == 0, "mul_mat_f: batch dims not broadcastable");
-    NEED(a->nb[0] == (int64_t)tsize(a->type) && b->nb[0] == 4, "mul_mat_f: k must be the contiguous dimension");
+// k_mul_mat_f on a call ggml_cdna4_op_mul_mat_f (gemm_f16.hip) has validated: F32 weights, and the F16 calls its plan leaves to this kernel
+int cdna4_launch_mul_mat_f(const T4 *a, const T4 *b, const T4 *d, hipStream_t st) {
     const int64_t nout = nelem(d);
     if (nout == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
     if (a->type == CDNA4_F32) hipLaunchKernelGGL(k_mul_mat_f<float>, grid1d(nout, 4), dim3(256), 0, st, *a, *b, *d, nout);
     else hipLaunchKernelGGL(k_mul_mat_f<half_t>, grid1d(nout, 4), dim3(256), 0, st, *a, *b, *d, nout);
     CDNA4_CHECK_LAUNCH();
     return 0;
 }
+extern "C" {
 
 int ggml_cdna4_op_rope(const T4 *a, const T4 *pos, const T4 *ffac, const T4 *d, int n_dims, int mode, int n_ctx_orig,
                        float freq_base, float freq_scale, float ext_factor, float attn_factor, float beta_fast, float beta_slow, void *stream) {

@@ -78,6 +78,8 @@ SYMBOLS = [
     ("ggml_cdna4_resident_image_unregister", _int, [_vp]),
     ("ggml_cdna4_resident_image_lookup", _int, [_int, _vp, _i64, _i64, _i64, C.POINTER(_vp)]),
 ]
+# include/ggml_cdna4_f16.h
+F16_SYMBOLS = [("ggml_cdna4_op_mul_mat_f_route", _int, [_vp, _vp, _vp])]
 
 
 class Tensor(C.Structure):
@@ -103,8 +105,8 @@ def lib():
         # in /opt/rocm's copy as a second runtime in the process.
         import torch  # noqa: F401
         l = C.CDLL(LIB_PATH)
-        for name, res, args in SYMBOLS:
-            fn = getattr(l, name)          # AttributeError if the .so does not export a declared symbol
+        for name, res, args in SYMBOLS + F16_SYMBOLS:
+            fn = getattr(l, name)         # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         if l.ggml_cdna4_api_version() != 1:
             raise NativeError("libcdna4_kernels.so API version mismatch")
