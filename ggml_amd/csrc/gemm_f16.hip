@@ -1,12 +1,14 @@
-// gemm_f16.hip — MUL_MAT on F16 weights (F32 activations rounded to fp16 first: vec_dot_type F16, ggml-cpu.c:7428-7605; fp32 accumulation) on the matrix cores,
-// and ggml_cdna4_op_mul_mat_f itself: validate, plan (gemm_f16_plan.hpp), execute.  Two kernels beside k_mul_mat_f (ops.hip), which keeps F32 weights and every
-// F16 call these two cannot read (K not a multiple of 8, src0 / src1 data or strides off 16 bytes):
-//   k_gemm_f16<TN>  128 x TN tiles (TN 32 / 128), K step 32, v_mfma_f32_32x32x16_f16 with the WEIGHTS as the A operand: a lane's four consecutive accumulator
-//                   values are four consecutive m, and a dst row is contiguous in m — 16-byte stores.  The weight tile goes from its fp16 rows straight into a
-//                   three-slot LDS ring by LDS-DMA, two stages ahead; the activation tile goes through registers (float4 loads issued before a stage's MFMAs,
-//                   rounded and written behind them), one stage ahead.  One barrier per K step.
+// gemm_f16.hip — MUL_MAT on F16 / BF16 weights (F32 activations rounded to the weight's format first: vec_dot_type F16, ggml-cpu.c:7428-7605, and BF16,
+// ggml-cpu.c:400-405; fp32 accumulation) on the matrix cores, and ggml_cdna4_op_mul_mat_f itself: validate, plan (gemm_f16_plan.hpp), execute.  Kernels beside
+// k_mul_mat_f (ops.hip), which keeps F32 weights and every F16 / BF16 call these cannot read (K not a multiple of 8, src0 / src1 data or strides off 16 bytes):
+//   k_gemm_f16<TN, BF>  128 x TN tiles (TN 32 / 128), K step 32, v_mfma_f32_32x32x16_f16 (BF: .._bf16, same shape and accumulator layout) with the WEIGHTS as the
+//                   A operand: a lane's four consecutive accumulator values are four consecutive m, and a dst row is contiguous in m — 16-byte stores.  The weight
+//                   tile goes from its 2-byte rows straight into a three-slot LDS ring by LDS-DMA, two stages ahead; the activation tile goes through registers
+//                   (float4 loads issued before a stage's MFMAs, rounded — BF: v_cvt_pk_bf16_f32 — and written behind them), one stage ahead.  One barrier per K step.
 //   k_gemv_f16<NB>  1 .. 8 activation rows: every wave streams TWO weight rows in 16-byte lane chunks (1 KB per wave load, eight loads in flight) against the NB
 //                   activation rows, rounded to fp16 once per work-group into LDS.
+//   k_gemv_bf16<NB> the same stream on bf16 rows with a loop of its own: a bf16 is the upper half of its fp32, so a weight dword becomes two fp32 by a shift and a mask
+//                   (once per chunk, shared by the NB rows), and the activations lie in LDS rounded to bf16 but already WIDENED to fp32 — the FMAs read them as they are.
 // LDS map of k_gemm_f16, per ring slot: [128 weight rows x 64 B][TN activation rows x 64 B]; a row holds its four 16-byte k-chunks at chunk ^ ((row >> 2) & 3),
 // so the sixteen lanes of a ds_read_b128 phase (rows r .. r + 15, one chunk) touch sixteen different 16-byte columns of the 256-byte bank window.
 #include "../../include/ggml_cdna4_f16.h"
@@ -17,9 +19,25 @@
 
 typedef ggml_cdna4_tensor T4;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+
+// the 2-byte element of a k_gemm_f16 instantiation: its vectors, and the matrix-core step on them
+template <bool BF> struct f16_elem { typedef half_t e; typedef half4_t v4; typedef half8_t v8; };
+template <> struct f16_elem<true> { typedef __bf16 e; typedef bf16x4_t v4; typedef bf16x8_t v8; };
+// four activations of a stage, rounded to nearest even (GGML_FP32_TO_FP16 / ggml_compute_fp32_to_bf16: no subnormal flush); past K (`in` false) zeros
+__device__ __forceinline__ void f16_round4(half4_t &h, const f32x4 &x, bool in) {
+#pragma unroll
+    for (int e = 0; e < 4; e++) h[e] = in ? (half_t)x[e] : (half_t)0.f;
+}
+__device__ __forceinline__ void f16_round4(bf16x4_t &h, const f32x4 &x, bool in) {      // as one vector: v_cvt_pk_bf16_f32 takes two values per instruction
+    h = __builtin_convertvector(in ? x : f32x4{0.f, 0.f, 0.f, 0.f}, bf16x4_t);
+}
+__device__ __forceinline__ floatx16 f16_mfma(half8_t a, half8_t b, floatx16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ floatx16 f16_mfma(bf16x8_t a, bf16x8_t b, floatx16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 
 struct f16_args {
-    const uint8_t *W; int64_t w_nb1, w_nb2, w_nb3;      // fp16 rows of K weights
+    const uint8_t *W; int64_t w_nb1, w_nb2, w_nb3;      // fp16 / bf16 rows of K weights
     const uint8_t *X; int64_t x_nb1, x_nb2, x_nb3;      // fp32 rows of K activations
     uint8_t *Y; int64_t y_nb1, y_nb2, y_nb3;            // Y[n][m], m contiguous
     int M, N, K;
@@ -29,8 +47,9 @@ struct f16_args {
 
 // ------------------------------------------------------------------------------------------------ the matrix-core GEMM
 #define F16_WST (F16_GEMM_TM * 64)                      // bytes of a weight stage: 128 rows x 32 halves
-template <int TN>
+template <int TN, bool BF>
 __global__ __launch_bounds__(256, 2) void k_gemm_f16(const f16_args p) {
+    typedef typename f16_elem<BF>::e elem_t; typedef typename f16_elem<BF>::v4 elem4_t; typedef typename f16_elem<BF>::v8 elem8_t;
     constexpr int XST = TN * 64, ST = F16_WST + XST, NST = 3;
     constexpr int NXL = TN / 32;                        // float4 loads per thread and stage
     constexpr int NBLK = TN == 128 ? 2 : 1;             // 32 x 32 blocks per wave and direction: a 64 x 64 / 32 x 32 wave tile
@@ -82,10 +101,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16(const f16_args p) {
         const bool in = s * 32 + 4 * (tid & 7) < K;
 #pragma unroll
         for (int i = 0; i < NXL; i++) {
-            half4_t h;
-#pragma unroll
-            for (int e = 0; e < 4; e++) h[e] = in ? (half_t)xr[i][e] : (half_t)0.f;      // round to nearest even, as GGML_FP32_TO_FP16
-            *(half4_t *)(smem + slot * ST + xlds[i]) = h;
+            elem4_t h;
+            f16_round4(h, xr[i], in);
+            *(elem4_t *)(smem + slot * ST + xlds[i]) = h;
         }
     };
 
@@ -122,15 +140,15 @@ __global__ __launch_bounds__(256, 2) void k_gemm_f16(const f16_args p) {
         const uint8_t *const ws = smem + slot * ST + wave_m * 64, *const xs = smem + slot * ST + F16_WST + wave_n * 64;
 #pragma unroll
         for (int j = 0; j < 2; j++) {
-            half8_t a[NBLK], b[NBLK];
+            elem8_t a[NBLK], b[NBLK];
 #pragma unroll
-            for (int bi = 0; bi < NBLK; bi++) a[bi] = *(const half8_t *)(ws + bi * 2048 + foff[j]);
+            for (int bi = 0; bi < NBLK; bi++) a[bi] = *(const elem8_t *)(ws + bi * 2048 + foff[j]);
 #pragma unroll
-            for (int bj = 0; bj < NBLK; bj++) b[bj] = *(const half8_t *)(xs + bj * 2048 + foff[j]);
+            for (int bj = 0; bj < NBLK; bj++) b[bj] = *(const elem8_t *)(xs + bj * 2048 + foff[j]);
 #pragma unroll
             for (int bi = 0; bi < NBLK; bi++)
 #pragma unroll
-                for (int bj = 0; bj < NBLK; bj++) acc[bi][bj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[bi], b[bj], acc[bi][bj], 0, 0, 0);
+                for (int bj = 0; bj < NBLK; bj++) acc[bi][bj] = f16_mfma(a[bi], b[bj], acc[bi][bj]);
         }
         if (nx) {
             // the activation loads are older than stage s + 2's two pieces; behind vmcnt(2) stage s + 1's weight pieces (older still) have landed too
@@ -226,6 +244,78 @@ __global__ __launch_bounds__(256) void k_gemv_f16(const f16_args p) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ 1 .. 8 activation rows, bf16 weights
+// LDS, per activation row: two planes of KC / 8 float4 — plane h holds k 4 h .. 4 h + 3 of every 8-k chunk, so the lanes of a wave (consecutive chunks) read
+// consecutive 16-byte pieces of a plane: no bank conflict.  NB x 8 KB.
+template <int NB>
+__global__ __launch_bounds__(256) void k_gemv_bf16(const f16_args p) {
+    constexpr int NCH = F16_GEMV_KC / 8;                                            // chunks (of eight k) per pass
+    __shared__ __attribute__((aligned(16))) uint8_t smem[NB * F16_GEMV_KC * 4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int row0 = blockIdx.x * F16_GEMV_ROWS + wave * 2;                         // this wave's two weight rows (past M: row M - 1, not stored)
+    const int i2 = (int)(blockIdx.z % (unsigned)p.ne2), i3 = (int)(blockIdx.z / (unsigned)p.ne2);
+    const uint8_t *const wbat = p.W + (int64_t)(i2 / p.r2) * p.w_nb2 + (int64_t)(i3 / p.r3) * p.w_nb3;
+    const uint8_t *const w0 = wbat + (int64_t)min(row0, p.M - 1) * p.w_nb1, *const w1 = wbat + (int64_t)min(row0 + 1, p.M - 1) * p.w_nb1;
+    const uint8_t *const xb = p.X + (int64_t)i2 * p.x_nb2 + (int64_t)i3 * p.x_nb3;
+    float acc0[NB], acc1[NB];
+#pragma unroll
+    for (int n = 0; n < NB; n++) acc0[n] = acc1[n] = 0.f;
+
+    for (int k0 = 0; k0 < p.K; k0 += F16_GEMV_KC) {
+        const int kc = min(F16_GEMV_KC, p.K - k0);
+        if (k0) __syncthreads();
+        // the NB activation rows of this pass, rounded to bf16 (nearest even, no subnormal flush) once per work-group and kept as fp32; a padding row repeats row N - 1
+#pragma unroll
+        for (int n = 0; n < NB; n++) {
+            const float *const xr = (const float *)(xb + (int64_t)min(n, p.N - 1) * p.x_nb1) + k0;
+            for (int q = tid; q < kc / 4; q += 256) {
+                const float4 v = *(const float4 *)(xr + 4 * q);
+                *(f32x4 *)(smem + ((n * 2 + (q & 1)) * NCH + (q >> 1)) * 16) = f32x4{(float)(__bf16)v.x, (float)(__bf16)v.y, (float)(__bf16)v.z, (float)(__bf16)v.w};
+            }
+        }
+        __syncthreads();
+        const int nch = kc / 8;                                                     // 16-byte chunks per row: lane l takes l, l + 64, ..
+        for (int c = lane; c < nch; c += 256) {
+            u32x4 wa[4], wc[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {                                           // all eight loads first; a chunk past the row reads chunk c again and is not used
+                const int cc = c + 64 * j < nch ? c + 64 * j : c;
+                wa[j] = ld_u32x4(w0 + (int64_t)(k0 + cc * 8) * 2); wc[j] = ld_u32x4(w1 + (int64_t)(k0 + cc * 8) * 2);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if (c + 64 * j >= nch) break;
+                // a bf16 is the upper half of its fp32: dword d holds weight 2 d in its low half (a shift) and weight 2 d + 1 in its high half (a mask)
+                float fa[8], fc[8];
+#pragma unroll
+                for (int d = 0; d < 4; d++) {
+                    fa[2 * d] = __builtin_bit_cast(float, wa[j][d] << 16); fa[2 * d + 1] = __builtin_bit_cast(float, wa[j][d] & 0xFFFF0000u);
+                    fc[2 * d] = __builtin_bit_cast(float, wc[j][d] << 16); fc[2 * d + 1] = __builtin_bit_cast(float, wc[j][d] & 0xFFFF0000u);
+                }
+#pragma unroll
+                for (int n = 0; n < NB; n++) {
+#pragma unroll
+                    for (int h = 0; h < 2; h++) {
+                        const f32x4 x = *(const f32x4 *)(smem + ((n * 2 + h) * NCH + c + 64 * j) * 16);
+#pragma unroll
+                        for (int e = 0; e < 4; e++) { acc0[n] = fmaf(fa[4 * h + e], x[e], acc0[n]); acc1[n] = fmaf(fc[4 * h + e], x[e], acc1[n]); }
+                    }
+                }
+            }
+        }
+    }
+    uint8_t *const yb = p.Y + (int64_t)i2 * p.y_nb2 + (int64_t)i3 * p.y_nb3;
+#pragma unroll
+    for (int n = 0; n < NB; n++) {
+        const float s0 = wave_sum_dpp(acc0[n]), s1 = wave_sum_dpp(acc1[n]);
+        if (lane == 0 && n < p.N) {
+            float *const yrow = (float *)(yb + (int64_t)n * p.y_nb1);
+            if (row0 < p.M) yrow[row0] = s0;
+            if (row0 + 1 < p.M) yrow[row0 + 1] = s1;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host
 static int f16_cu_count() {                                        // of the current device; without one CDNA4_ASSUME_CUS names the part (the route query on the CPU)
     int dev = 0;
@@ -249,9 +339,22 @@ static int f16_run(const f16_plan &pl, const T4 *a, const T4 *b, const T4 *d, hi
     p.y16 = pl.y16 ? 1 : 0;
     p.ne2 = (int)d->ne[2]; p.r2 = (int)(b->ne[2] / a->ne[2]); p.r3 = (int)(b->ne[3] / a->ne[3]);
     const dim3 grid(pl.gx, pl.gy, pl.gz);
+    const bool bf = a->type == CDNA4_BF16;
     if (pl.route == F16_GEMM) {
-        if (pl.tn == 128) hipLaunchKernelGGL(k_gemm_f16<128>, grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(k_gemm_f16<32>, grid, dim3(256), 0, st, p);
+        if (bf) {
+            if (pl.tn == 128) hipLaunchKernelGGL((k_gemm_f16<128, true>), grid, dim3(256), 0, st, p);
+            else hipLaunchKernelGGL((k_gemm_f16<32, true>), grid, dim3(256), 0, st, p);
+        } else {
+            if (pl.tn == 128) hipLaunchKernelGGL((k_gemm_f16<128, false>), grid, dim3(256), 0, st, p);
+            else hipLaunchKernelGGL((k_gemm_f16<32, false>), grid, dim3(256), 0, st, p);
+        }
+    } else if (bf) {
+        switch (pl.nb) {
+            case 1: hipLaunchKernelGGL(k_gemv_bf16<1>, grid, dim3(256), 0, st, p); break;
+            case 2: hipLaunchKernelGGL(k_gemv_bf16<2>, grid, dim3(256), 0, st, p); break;
+            case 4: hipLaunchKernelGGL(k_gemv_bf16<4>, grid, dim3(256), 0, st, p); break;
+            default: hipLaunchKernelGGL(k_gemv_bf16<8>, grid, dim3(256), 0, st, p); break;
+        }
     } else {
         switch (pl.nb) {
             case 1: hipLaunchKernelGGL(k_gemv_f16<1>, grid, dim3(256), 0, st, p); break;

@@ -1,4 +1,4 @@
-// gemm_f16_plan.hpp — the routing plan of ggml_cdna4_op_mul_mat_f (gemm_f16.hip): which kernel a MUL_MAT on F32 / F16 weights takes and the launch geometry.
+// gemm_f16_plan.hpp — the routing plan of ggml_cdna4_op_mul_mat_f (gemm_f16.hip): which kernel a MUL_MAT on F32 / F16 / BF16 weights takes and the launch geometry.
 // f16_make_plan() is side-effect free — no launch, no error text; it reads the three tensor descriptors, the CU count and ONE env knob (CDNA4_F16_GEMM=0:
 // the new kernels are off, for A/B timing) — so the call and ggml_cdna4_op_mul_mat_f_route read the SAME plan: the call executes it, the query reads `route`.
 // Host-only; kernel-library sources only (like gemm_q_plan.hpp: not one of the files the ggml plug-in's checksum covers).
@@ -10,9 +10,9 @@
 enum f16_route {
     F16_REFUSED = 0,    // the call returns -1 with the message `err`
     F16_PLAIN = 1,      // k_mul_mat_f (ops.hip): one wave per output element; F32 weights, and whatever the kernels below cannot read
-    F16_GEMV = 2,       // k_gemv_f16<nb>: 1 .. 8 activation rows, bound by the weight stream
-    F16_GEMM = 3,       // k_gemm_f16<tn>: the matrix cores
-};
+    F16_GEMV = 2,       // k_gemv_f16<nb> / k_gemv_bf16<nb>: 1 .. 8 activation rows, bound by the weight stream
+    F16_GEMM = 3,       // k_gemm_f16<tn, bf>: the matrix cores
+};                      // (the two 2-byte weight types route alike; for BF16 src0 a number names the bf16 instantiation)
 struct f16_plan {
     int route; const char *err;
     bool empty;         // nothing to multiply: the call returns 0 without a launch
@@ -32,14 +32,14 @@ int cdna4_launch_mul_mat_f(const ggml_cdna4_tensor *a, const ggml_cdna4_tensor *
 inline f16_plan f16_make_plan(const ggml_cdna4_tensor *a, const ggml_cdna4_tensor *b, const ggml_cdna4_tensor *d, int cus) {
     f16_plan pl{};
     auto refuse = [&](const char *msg) { pl.route = F16_REFUSED; pl.err = msg; return pl; };
-    if (!((a->type == CDNA4_F32 || a->type == CDNA4_F16) && b->type == CDNA4_F32 && d->type == CDNA4_F32)) return refuse("mul_mat_f: F32/F16 x F32 only");
+    if (!((a->type == CDNA4_F32 || a->type == CDNA4_F16 || a->type == CDNA4_BF16) && b->type == CDNA4_F32 && d->type == CDNA4_F32)) return refuse("mul_mat_f: F32/F16/BF16 x F32 only");
     if (!(a->ne[0] == b->ne[0] && d->ne[0] == a->ne[1] && d->ne[1] == b->ne[1] && d->ne[2] == b->ne[2] && d->ne[3] == b->ne[3])) return refuse("mul_mat_f: shape mismatch");
     if (!(a->ne[2] > 0 && a->ne[3] > 0 && b->ne[2] % a->ne[2] == 0 && b->ne[3] % a->ne[3] == 0)) return refuse("mul_mat_f: batch dims not broadcastable");
     if (!(a->nb[0] == (a->type == CDNA4_F32 ? 4 : 2) && b->nb[0] == 4)) return refuse("mul_mat_f: k must be the contiguous dimension");
     pl.route = F16_PLAIN;
     const int64_t M = d->ne[0], N = d->ne[1], K = a->ne[0], nbatch = d->ne[2] * d->ne[3];
     pl.empty = M * N * nbatch == 0;
-    if (pl.empty || a->type != CDNA4_F16) return pl;
+    if (pl.empty || a->type == CDNA4_F32) return pl;
     const char *knob = getenv("CDNA4_F16_GEMM");
     if (knob && atoi(knob) == 0) return pl;
     // what the new kernels read: 16-byte chunks of eight weights (LDS-DMA / wave loads) and float4 activations; they write dst rows contiguous in m

@@ -419,7 +419,12 @@ __global__ __launch_bounds__(256) void k_cpy_f32_to_q45(const T4 a, const T4 d, 
     if (FIVE) { uint8_t *ph = out + (MINMAX ? 4 : 2); *(uint16_t *)ph = (uint16_t)qh; *(uint16_t *)(ph + 2) = (uint16_t)(qh >> 16); }
 }
 
-// ------------------------------------------------------------------------------------------------ mul_mat F32/F16
+// ------------------------------------------------------------------------------------------------ mul_mat F32/F16/BF16
+// src1 as the weight type's vec_dot_type sees it: F32 as it is, F16 / BF16 rounded to the weight's format first (nearest even; bf16 without a subnormal flush,
+// ggml_compute_fp32_to_bf16)
+__device__ __forceinline__ float mmf_round_x(float v, const float *) { return v; }
+__device__ __forceinline__ float mmf_round_x(float v, const half_t *) { return (float)(half_t)v; }
+__device__ __forceinline__ float mmf_round_x(float v, const __bf16 *) { return (float)(__bf16)v; }
 // one wave per output element (m, n, batch): lanes stride over k (both operands contiguous in k)
 template <typename TW>
 __global__ __launch_bounds__(256) void k_mul_mat_f(const T4 a, const T4 b, const T4 d, int64_t nout) {
@@ -433,9 +438,8 @@ __global__ __launch_bounds__(256) void k_mul_mat_f(const T4 a, const T4 b, const
     float s = 0.f;
     const int K = (int)a.ne[0];
     for (int k = lane; k < K; k += 64) {
-        float xv = v[k];
-        if (sizeof(TW) == 2) xv = (float)(half_t)xv;                  // vec_dot_type F16: src1 is rounded to fp16 first
-        s = fmaf((float)w[k], xv, s);
+        const float xv = mmf_round_x(v[k], w);                         // vec_dot_type F16 / BF16: src1 is rounded to the weight's format first
+        s = fmaf((float)w[k], xv, s);                                  // (a bf16 weight widens exactly: its 16 bits are the upper half of the fp32)
     }
     s = wave_sum(s);
     if (lane == 0) *(float *)at(d, x) = s;
@@ -711,11 +715,12 @@ int cdna4_launch_to_f16_dense(const T4 *a, void *dst, int64_t dst_row, hipStream
     CDNA4_CHECK_LAUNCH();
     return 0;
 }
-// k_mul_mat_f on a call ggml_cdna4_op_mul_mat_f (gemm_f16.hip) has validated: F32 weights, and the F16 calls its plan leaves to this kernel
+// k_mul_mat_f on a call ggml_cdna4_op_mul_mat_f (gemm_f16.hip) has validated: F32 weights, and the F16 / BF16 calls its plan leaves to this kernel
 int cdna4_launch_mul_mat_f(const T4 *a, const T4 *b, const T4 *d, hipStream_t st) {
     const int64_t nout = nelem(d);
     if (nout == 0) return 0;
     if (a->type == CDNA4_F32) hipLaunchKernelGGL(k_mul_mat_f<float>, grid1d(nout, 4), dim3(256), 0, st, *a, *b, *d, nout);
+    else if (a->type == CDNA4_BF16) hipLaunchKernelGGL(k_mul_mat_f<__bf16>, grid1d(nout, 4), dim3(256), 0, st, *a, *b, *d, nout);
     else hipLaunchKernelGGL(k_mul_mat_f<half_t>, grid1d(nout, 4), dim3(256), 0, st, *a, *b, *d, nout);
     CDNA4_CHECK_LAUNCH();
     return 0;

@@ -216,6 +216,26 @@ static inline emu_floatx16 emu_mfma_32x32x16_f16(emu_half8 a, emu_half8 b, emu_f
     return c;
 }
 #define __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, x, y, z) emu_mfma_32x32x16_f16(a, b, c)
+// v_mfma_f32_32x32x16_bf16: the same lanes, operands and accumulator layout on bf16 (staged as their 16-bit patterns; a bf16 is the upper half of its fp32)
+typedef __bf16 emu_bf16x8 __attribute__((ext_vector_type(8)));
+static inline emu_floatx16 emu_mfma_32x32x16_bf16(emu_bf16x8 a, emu_bf16x8 b, emu_floatx16 c) {
+    emu::WaveState &w = emu::my_wave();
+    const int l = emu::t_threadIdx.x & 63;
+    memcpy(&w.A[l][0], &a, 16); memcpy(&w.B[l][0], &b, 16);
+    pthread_barrier_wait(&w.bar);
+    const int n = l & 31, hh = l >> 5;
+    auto widen = [](const _Float16 &h) { uint16_t u; memcpy(&u, &h, 2); const uint32_t v = (uint32_t)u << 16; float f; memcpy(&f, &v, 4); return f; };
+    for (int r = 0; r < 16; r++) {
+        const int i = (r & 3) + 8 * (r >> 2) + 4 * hh;
+        float s = 0.f;
+        for (int kh = 0; kh < 2; kh++)
+            for (int e = 0; e < 8; e++) s += widen(w.A[i + 32 * kh][e]) * widen(w.B[n + 32 * kh][e]);
+        c[r] += s;
+    }
+    pthread_barrier_wait(&w.bar);
+    return c;
+}
+#define __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, x, y, z) emu_mfma_32x32x16_bf16(a, b, c)
 // v_mfma_i32_16x16x32_i8, wave-collective: lane l supplies A[row l % 16][k 8 (l / 16) .. + 7] and B[k ..][col l % 16] (eight int8 in a 64-bit
 // operand each) and receives D[row 4 (l / 16) + v][col l % 16] for v = 0 .. 3
 typedef int emu_intx4 __attribute__((ext_vector_type(4)));
