@@ -5,6 +5,7 @@
 #include "cdna4_kernels.h"
 #include "gemm_q_plan.hpp"
 #include "mul_mat_id_plan.hpp"
+#include "moe_f16_plan.hpp"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -125,6 +126,7 @@ size_t ggml_cdna4_mul_mat_workspace_size(int type, int64_t K, int64_t n_act_rows
 }
 
 size_t ggml_cdna4_mul_mat_id_workspace_size(int type, int64_t K, int64_t n_expert, int64_t n_used, int64_t n_b, int64_t n_tok) {
+    if (type == CDNA4_F16 || type == CDNA4_BF16) return moe_f16_workspace_size(K, n_expert, n_used, n_b, n_tok);      // the planner's row lists and tile tables; no activation image
     if (!cdna4_type_qk(type) || K <= 0 || n_tok <= 0 || n_used <= 0 || n_b <= 0 || n_expert <= 0) return 0;
     const size_t plain = carve(type, K, n_tok * n_b, nullptr).total;
     if (!cdna4_gemm_ids_supported(type, K) || n_tok * n_used <= 32) return plain;
@@ -614,6 +616,8 @@ mmid_plan mmid_make_plan(const mmid_call &c, bool front_in_place) {
 
 static int mul_mat_id_impl(const mmid_call &c, bool front_in_place, void *stream) {
     if (const int frc = fault_status()) return frc;
+    // F16 / BF16 expert stacks: a plan and kernels of their own (moe_f16_plan.hpp, moe_f16.hip); mmid_make_plan is about the quantized formats
+    if (!front_in_place && (c.type == CDNA4_F16 || c.type == CDNA4_BF16)) return cdna4_mul_mat_id_f16(c, (hipStream_t)stream);
     const mmid_plan p = mmid_make_plan(c, front_in_place);
     if (p.kind == MMID_REFUSED) { cdna4_set_error_msg(p.err); return p.rc; }
     hipStream_t st = (hipStream_t)stream;

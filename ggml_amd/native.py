@@ -79,7 +79,8 @@ SYMBOLS = [
     ("ggml_cdna4_resident_image_lookup", _int, [_int, _vp, _i64, _i64, _i64, C.POINTER(_vp)]),
 ]
 # include/ggml_cdna4_f16.h
-F16_SYMBOLS = [("ggml_cdna4_op_mul_mat_f_route", _int, [_vp, _vp, _vp])]
+F16_SYMBOLS = [("ggml_cdna4_op_mul_mat_f_route", _int, [_vp, _vp, _vp]),
+               ("ggml_cdna4_mul_mat_id_f16_route", _int, [_int, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _sz])]
 
 
 class Tensor(C.Structure):
