@@ -77,6 +77,11 @@ SELECTION_R3.append(("test_gpu_moe_plan.py", "(several_rounds and 1025 and not h
 # (The 65536-row expert is left to the GPU: ~4,100 quantizer work-groups and 516 tiles, each emulated work-group a process.)
 SELECTION_R3.append(("test_gpu_moe_plan.py", "record_window and 256-4", 1, {"EMU_CUS": "4"}))
 SELECTION_R3.append(("test_gpu_moe_plan.py", "record_window and 768-3", 1, {"EMU_CUS": "3"}))
+# MUL_MAT on F16 / BF16 weights: the shared matrix-core tile body and few-row stream of gemm_f16_dev.hpp through their dense callers — one tile and one step; ragged M and N
+# with a K tail of 8; 1 / 2 / 3 / 8 activation rows at K 24 (every NB instantiation).  (The MUL_MAT_ID callers, tests/test_gpu_mul_mat_id_f16.py, are left to the GPU: their
+# route query is one of native.F16_SYMBOLS, which tests/emul_torch.py does not bind on the emulated library, so its 64-bit arguments arrive cut to 32.)
+SELECTION_R3.append(("test_gpu_mul_mat_f16.py", "(test_f16_gemm_route and (128-32-32 or 130-40-33)) or (test_f16_few_row_route and 37-24)", 6))
+SELECTION_R3.append(("test_gpu_mul_mat_bf16.py", "128-32-32 or 130-40-33 or 37-24-", 6))
 
 
 def _merged(selections):

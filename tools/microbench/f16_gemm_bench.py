@@ -1,5 +1,5 @@
 """A/B timing of ggml_cdna4_op_mul_mat_f on F16 / BF16 weights: CDNA4_F16_GEMM=0 (k_mul_mat_f, one wave per output element) against the default plan
-(k_gemv_f16 / k_gemv_bf16 / k_gemm_f16, ggml_amd/csrc/gemm_f16.hip), alternating the two per shape, device events around a batch of calls.
+(k_gemv_f16 / k_gemm_f16, ggml_amd/csrc/gemm_f16.hip), alternating the two per shape, device events around a batch of calls.
 
     python tools/microbench/f16_gemm_bench.py [--type f16|bf16|both] [out.txt]
 
